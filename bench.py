@@ -9,7 +9,14 @@ importance → quantization → selective propagation) through the C ABI's fused
 (rtkv_compress_layer: 3 kernels per layer, no host sync inside the step).  Inputs are synthetic
 (seeded, resident in HBM before timing).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it sets up the inputs, warms up, times the K steps,
+writes the last step's outputs when ``--dump-outputs DIR`` is given (dump_outputs() below) and prints the
+result line (``value``, ``ms_per_step`` and the description of the workload).  Everything else this file
+measures runs only with ``--full``: the per-kernel event times and the two roofline objects, the extra legs
+(``--legs``), the CPU baseline, and at N > 1 the per-rank compute / all-gather / exchange split and the
+same-workload single-GPU reference.
 
 Workloads (BASELINE.json configs): cfg3 (Llama-2-7B, 32 layers, S = 16384; the N = 1 default and
 the headline), cfg4 (Llama-2-7B, S = 65536 in total; the N > 1 default) and cfg5 (Llama-2-13B,
@@ -21,7 +28,8 @@ starts ``python -m torch.distributed.run --nproc-per-node N ... bench.py ...`` a
 before anything touches a GPU, waits for it and exits with its code; it fails at once when fewer
 than N GPUs are visible.  ``--launch-dry-run`` prints that command line and exits.
 
-Rank 0 prints ONE JSON line.  ``value`` = algorithmic bytes of the whole job ÷ wall time (GB/s);
+Rank 0 prints ONE JSON line (the fields from ``roofline`` on: with ``--full``).
+``value`` = algorithmic bytes of the whole job ÷ wall time (GB/s);
 ``ttft_ms`` = the step's wall time with every layer strictly after the previous one (the reference
 caller's order: layer l+1's K/V come out of attention over layer l's compressed K'/V',
 modified_llama.py:113-157), i.e. Σ per-layer compress time;
@@ -188,6 +196,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times and rooflines, the extra "
+                         "legs (--legs), the CPU baseline, at N > 1 the per-rank split and the same-workload "
+                         "single-GPU reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (single GPU)")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="BASELINE workload: cfg3 (default at N = 1), cfg4 (default at N > 1) or cfg5")
     ap.add_argument("--layers", type=int, default=None, help="override the config's layer count")
@@ -866,6 +880,65 @@ def kernel_us(job, kus):
     return {"K1_aggregation": round(kus[0], 2), "K2_select": round(kus[1], 2), "K4_quant_pack": round(kus[2], 2)}
 
 
+DUMP_BUDGET = 64 * 10 ** 6  # bytes of .npy data a --dump-outputs run may write
+
+
+def dump_outputs(job, out_dir, budget=DUMP_BUDGET):
+    """Write what the last timed step left in the layers' output buffers (what a caller of
+    rtkv.compress_layer reads) as out_dir/<name>.npy, float32 (float64 where float32 cannot hold the
+    integers), within ``budget`` bytes.  Nothing is computed again: the buffers are read as they stand.
+
+    Leading axis: the layers whose outputs are still resident (``layers.npy``; with fewer output slots
+    than layers, each slot's last layer).  Per-token arrays over the token positions ``tokens.npy`` (all
+    S of them unless the budget asks for a seeded sample): scores, labels, mask; and over the kept-row
+    slots at the same positions (slot j of a layer is valid for j < kept_rows[layer]; the padding is -1,
+    0 for scale_zp): kept_index, row_offset, scale_zp.  ``k_out_sample`` / ``v_out_sample`` /
+    ``packed_k_sample`` / ``packed_v_sample``: the elements (bytes) at seeded positions
+    floor(u * valid length) of the dequantized rows (kept_rows * F elements) and the packed codes
+    (packed_bytes bytes).  The positions depend on the run's arguments and a fixed seed only."""
+    import numpy as np
+    from rtkv.engine import decode_stats
+    os.makedirs(out_dir, exist_ok=True)
+    layers = [l for l in range(job.args.layers) if l + job.slots >= job.args.layers]
+    n, S = len(layers), job.S
+    rng = np.random.RandomState(20251019)
+    # as stored, a token costs 40 bytes per layer (4 float32 arrays, one float64, scale_zp's 4 float32):
+    # 5/8 of the budget for those, 1/4 for the four sampled arrays
+    T = min(S, budget * 5 // 8 // (40 * n + 8))
+    tok = np.arange(S) if T == S else np.sort(rng.choice(S, T, replace=False))
+    m = min(32768, budget // 4 // (16 * n))
+    u = rng.random_sample(m)
+    tok_dev = torch.from_numpy(tok).to(job.device)
+    out = {"layers": np.asarray(layers, np.float64), "tokens": tok.astype(np.float64),
+           "kept_rows": np.zeros(n), "packed_bytes": np.zeros(n)}
+    per_token = ["scores", "labels", "mask"]
+    per_slot = ["kept_index"] + (["row_offset", "scale_zp"] if job.emit_packed else [])
+    sampled = (["k_out", "v_out"] if job.emit_dequant else []) + (["packed_k", "packed_v"] if job.emit_packed else [])
+    for name in per_token + per_slot:
+        out[name] = np.zeros((n, T, 4) if name == "scale_zp" else (n, T),
+                             np.float64 if name == "row_offset" else np.float32)
+    for name in sampled:
+        out[name + "_sample"] = np.zeros((n, m), np.float32)
+    for i, l in enumerate(layers):
+        b = job.bufs[l % job.slots]
+        st = decode_stats(b.stats.cpu().numpy().tobytes(), 1)
+        Sp, pk = int(st.max_kept), int(st.total_packed_bytes)
+        out["kept_rows"][i], out["packed_bytes"][i] = Sp, pk
+        for name in per_token + per_slot:
+            a = getattr(b, name)[0][tok_dev].cpu().numpy().astype(out[name].dtype)
+            if name in per_slot:
+                a[tok >= Sp] = 0 if name == "scale_zp" else -1
+            out[name][i] = a
+        for name in sampled:
+            valid = pk if name.startswith("packed") else Sp * job.F
+            if valid:
+                pos = torch.from_numpy(np.minimum((u * valid).astype(np.int64), valid - 1)).to(job.device)
+                out[name + "_sample"][i] = getattr(b, name)[pos].float().cpu().numpy()
+    assert sum(a.nbytes for a in out.values()) <= budget
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -879,6 +952,8 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE {world}: refusing a mislabelled run", file=sys.stderr)
         sys.exit(2)
     resolve_config(args, world)
+    if args.dump_outputs and (world > 1 or args.sharded):
+        raise SystemExit("bench.py: --dump-outputs writes the single-GPU driver's outputs; not with the sharded driver")
     if args.dist_backend == "gloo":  # rehearsal: ranks may share the visible GPUs
         local = local % max(1, torch.cuda.device_count())
         args.collectives = "host"
@@ -923,15 +998,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(job, args.dump_outputs)  # the last timed step's outputs, before anything runs again
 
     kus = None
-    split = None
-    if sharded:
+    split = {}
+    if sharded and args.full:
         for _ in range(2):
             job.step()
         torch.cuda.synchronize(device)
         split = job.split_times(barrier)  # per-rank compute / all-gather / exchange, outside the timed loop
-    else:
+    elif args.full:
         kus = job.kernel_times()  # per-kernel timing (HIP events on the launch stream), outside the timed loop
     tot_bytes, k4_bytes = job.layer_bytes()
     step_bytes = sum(tot_bytes)  # whole-job algorithmic bytes (the sharded job counts all N*S tokens)
@@ -946,7 +1023,7 @@ def main():
         ranks = [None] * world
         dist.all_gather_object(ranks, me)
     single = None
-    if sharded and world > 1 and rank == 0 and not args.no_same_workload:
+    if args.full and sharded and world > 1 and rank == 0 and not args.no_same_workload:
         # the SAME S_total prefill through the single-GPU driver on this GPU (the other ranks wait in the
         # final barrier): the per-N lines of a 1 -> N curve then each carry their own same-workload time
         ref = Job(args, device, 0, 1, inputs=union_inputs(args, device, world, job.dtype), seq=args.seq * world,
@@ -999,7 +1076,7 @@ def main():
                                           "each issued two layers later on its own communicator, overlapping "
                                           "the following layers' compute")),
                                 "per_layer_collective": "RCCL all-gather of A (4 B/token)"}
-        else:
+        elif args.full:
             path, k4 = roofline_objects(args, job, kus, k4_bytes)
             line["roofline"] = k4  # the contract's object: the dominant kernel (K4) on its algorithmic bytes
             line["roofline_path"] = path  # the north star's: the whole layer path on its HBM-read bytes

@@ -4,7 +4,7 @@ bench.py process, since the library reads its knobs once per process).
 
     python tools/ab_env.py TAG --rounds 2 --variants 'A=' 'B=RTKV_K4_PK_WAVES=4' -- --dtype float16 --no-dequant
 
-Every run: bench.py --legs none (unless --legs is among the arguments) --cpu-baseline-seconds 0 plus the
+Every run: bench.py --full --legs none (unless --legs is among the arguments) --cpu-baseline-seconds 0 plus the
 arguments after '--'.  Writes
 gpurun_out/ab_TAG.json with, per variant, every run's ms_per_step and per-kernel event times, and the
 means; prints one summary line per variant.
@@ -43,7 +43,8 @@ def main():
         for name, env in variants:
             e = dict(os.environ, **env)
             legs = [] if "--legs" in bench_args else ["--legs", "none"]
-            cmd = [sys.executable, os.path.join(REPO, "bench.py"), *legs, "--cpu-baseline-seconds", "0", *bench_args]
+            cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", *legs, "--cpu-baseline-seconds", "0",
+                   *bench_args]
             p = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=a.timeout)
             if p.returncode != 0:
                 print(f"{name}: rc={p.returncode}\n{p.stderr[-2000:]}", flush=True)

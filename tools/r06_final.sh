@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 1700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1 || exit 1
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 1
-timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py --legs none --cpu-baseline-seconds 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $B --steps 5 --warmup 2 > $O/prof.log 2>&1 || exit 1

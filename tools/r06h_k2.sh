@@ -6,4 +6,4 @@ mkdir -p $O
 for a in "16384 0.6" "16384 1.0" "4096 0.6" "4096 1.0" "65536 0.6"; do
   timeout -k 10 120 ./tools/k2_probe $a > $O/k2probe_$(echo $a | tr ' ' _).txt 2>&1 || exit 1
 done
-[ -n "${SKIP_BENCH:-}" ] || timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || exit 1
+[ -n "${SKIP_BENCH:-}" ] || timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
