@@ -565,6 +565,45 @@ int rtkv_decode_attention_packed(const uint8_t* packed_k_dev, const uint8_t* pac
                                  const int32_t bits[3], const void* q_dev, int64_t Hq, float scale,
                                  float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The dense K/V rows of the tokens generated after the prefill (one layer): element (b, t, h, d) of
+ * k_dev / v_dev lies at b*stride_b + t*stride_s + h*D + d (strides in elements of the K/V dtype,
+ * heads contiguous, stride_s >= Hkv*D), for t < rows_dev[b] <= capacity.  k_dev, v_dev and both
+ * strides keep every row 16-byte aligned.  rows_dev is read on the device (a count outside
+ * [0, capacity] is clamped), so a generation loop appends without a host round trip. */
+typedef struct rtkv_dense_tail {
+  const void* k_dev;
+  const void* v_dev;
+  const int64_t* rows_dev;   /* [B] tail rows in use */
+  int64_t capacity;          /* rows allocated per batch row */
+  int64_t stride_b;
+  int64_t stride_s;
+} rtkv_dense_tail;
+
+/* Decode attention over one layer's PACKED KV followed by a dense tail: a decode step of the
+ * reference (q_len == 1) does not compress, it concatenates the new token's K/V onto the cache and
+ * attends over all of it (modified_llama.py:83-94, 152), so at step t the keys are the kept,
+ * dequantized prefill rows and then the t dense rows generated so far.  out[b,h,:] =
+ * softmax_j(q[b,h]·X[b,j,h/G]ᵀ·scale)·Y[b,j,h/G] with X/Y = K'/V' decoded from the packed codes for
+ * j < rows[b] (exactly as rtkv_decode_attention_packed) followed by the tail's rows_dev[b] rows as
+ * stored: one softmax over the concatenation, stream-ordered, no host synchronisation.  Every
+ * argument of rtkv_decode_attention_packed with the same meaning and the same envelope (F = Hkv·D a
+ * multiple of 512, head_dim 8·2^k <= 512, field widths 2/4/8/16, all three dtypes), plus the tail.
+ * row_capacity == 0 is allowed (attention over the tail alone; the packed pointers and bits may then
+ * be null); a batch row with no packed row and no tail row gives zeros.  With an empty tail the
+ * result has the bits of rtkv_decode_attention_packed.  Workspace:
+ * rtkv_decode_tail_workspace_size(B, Hq, Hkv, D, row_capacity, tail->capacity) bytes.
+ * RTKV_ERR_INVALID ("decode: ..."): a misaligned tail base or stride, a negative capacity, a null
+ * rows_dev, a too-small workspace. */
+size_t rtkv_decode_tail_workspace_size(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t row_capacity,
+                                       int64_t tail_capacity);
+int rtkv_decode_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t* packed_v_dev, int64_t packed_bytes,
+                                      const int64_t* row_offset_dev, const float* scale_zp_dev,
+                                      const int32_t* kept_index_dev, const uint8_t* labels_dev, int64_t B, int64_t S,
+                                      int64_t row_capacity, const int64_t* rows_dev, int64_t Hkv, int64_t D, int dtype,
+                                      const int32_t bits[3], const void* q_dev, int64_t Hq, float scale,
+                                      const rtkv_dense_tail* tail, float* out_dev, void* workspace_dev,
+                                      size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Extension "rtkv-gq/1": per-channel outlier detection + per-head group-wise 2/4/8-bit pack.
  * NO REFERENCE COUNTERPART — the reference quantizes each token with one (scale, zero_point) over all H·D

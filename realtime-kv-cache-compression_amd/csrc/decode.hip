@@ -49,39 +49,6 @@ __global__ __launch_bounds__(kMF * kMP) void decode_merge_kernel(DecodeArgs a) {
   a.out[((int64_t)b * Hq + (int64_t)hk * a.G + g) * a.D + d] = den > 0.f ? num / den : 0.f;
 }
 
-// Per-lane shape: GQ query heads of a kv head share each decoded K'/V' chunk; NCH chunks per lane
-// (GQ · NCH ≤ 4 keeps the accumulators at ≤ 32 VGPRs).
-struct DecodeShape {
-  int nch, gq, hg, gs;
-};
-DecodeShape decode_shape(int64_t F, int64_t G) {
-  DecodeShape d;
-  d.gq = G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1);
-  d.nch = ((F / 512) % 2 == 0 && d.gq == 1) ? 2 : 1;
-  d.hg = (int)(F / 512) / d.nch;
-  d.gs = (int)(G / d.gq);
-  return d;
-}
-
-int decode_target_wgs() {
-  static const int t = [] {
-    const char* e = std::getenv("RTKV_DECODE_WGS");  // tuning knob, default 1024 workgroups
-    const int v = e ? std::atoi(e) : 0;
-    return v > 0 ? v : 1024;
-  }();
-  return t;
-}
-
-int decode_splits(int64_t B, int64_t G, int64_t F, int64_t cap) {
-  const DecodeShape d = decode_shape(F, G);
-  int64_t s = (cap + 16 * kDW - 1) / (16 * kDW);    // at least ~16 rows per wave
-  const int64_t wg = B * d.gs * (d.hg > 0 ? d.hg : 1);
-  const int64_t target = decode_target_wgs() / (wg > 0 ? wg : 1);
-  if (s > target) s = target;
-  if (s < 1) s = 1;
-  return (int)s;
-}
-
 }  // namespace
 
 size_t decode_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t cap) {
@@ -90,11 +57,11 @@ size_t decode_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int
   return (size_t)(B * G * s) * (size_t)(2 * Hkv + Hkv * D) * sizeof(float) + 256;
 }
 
-int launch_decode(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                  const float* scale_zp,
-                  const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S, int64_t cap,
-                  const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
-                  int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_decode_splits(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
+                         const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
+                         int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3],
+                         const void* q, int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                         DecodeArgs& a) {
   RTKV_REQUIRE(codes_k && codes_v && row_offset && scale_zp && kept_index && labels && rows && q && out,
                "decode: null pointer");
   RTKV_REQUIRE(B >= 1 && S >= 1 && cap >= 1 && Hkv >= 1 && D >= 1 && Hq >= Hkv && Hq % Hkv == 0,
@@ -104,7 +71,6 @@ int launch_decode(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_
   const int64_t G = Hq / Hkv;
   RTKV_REQUIRE(F % 512 == 0, "decode: Hkv*D must be a multiple of 512");
   RTKV_REQUIRE(D % 8 == 0 && 64 % (D / 8) == 0, "decode: head_dim must be 8·2^k with 8 <= head_dim <= 512");
-  DecodeArgs a;
   std::memset(&a, 0, sizeof(a));
   for (int k = 0; k < 3; ++k) {
     a.w[k] = field_width(dt, bits[k]);
@@ -138,7 +104,19 @@ int launch_decode(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_
   if (dt == RTKV_F16) rc = launch_decode_split_f16(a, sh.nch, sh.gq, (int)D, grid, lds, st);
   else if (dt == RTKV_BF16) rc = launch_decode_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
   else rc = launch_decode_split<RTKV_F32>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
+  return rc;
+}
+
+int launch_decode(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
+                  const float* scale_zp,
+                  const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S, int64_t cap,
+                  const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
+                  int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  DecodeArgs a;
+  const int rc = launch_decode_splits(codes_k, codes_v, codes_bytes, row_offset, scale_zp, kept_index, labels, B, S, cap,
+                                      rows, Hkv, D, dt, bits, q, Hq, scale, out, ws, ws_bytes, st, a);
   if (rc != RTKV_OK) return rc;
+  const int64_t F = Hkv * D, G = Hq / Hkv;
   hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)((F + kMF - 1) / kMF), (unsigned)G, (unsigned)B),
                      dim3(kMF * kMP), 0, st, a);
   RTKV_HIP_CHECK(hipGetLastError());

@@ -58,7 +58,50 @@ struct DecodeArgs {
 // launches decode_split_kernel<RTKV_F16, …> (decode_f16.hip, its own flags)
 int launch_decode_split_f16(const DecodeArgs& a, int nch, int gq, int D, dim3 grid, size_t lds, hipStream_t st);
 
+// The packed half of a decode step without the merge (decode.hip): checks the arguments, fills `a`
+// with the partials laid out at the start of ws and launches the split kernels.  launch_decode
+// merges them; the dense-tail entry point (decode_tail.hip) merges them with the tail's partials.
+int launch_decode_splits(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
+                         const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
+                         int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3],
+                         const void* q, int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                         DecodeArgs& a);
+
 namespace {
+
+// Per-lane shape: GQ query heads of a kv head share each decoded K'/V' chunk; NCH chunks per lane
+// (GQ · NCH ≤ 4 keeps the accumulators at ≤ 32 VGPRs).
+struct DecodeShape {
+  int nch, gq, hg, gs;
+};
+inline DecodeShape decode_shape(int64_t F, int64_t G) {
+  DecodeShape d;
+  d.gq = G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1);
+  d.nch = ((F / 512) % 2 == 0 && d.gq == 1) ? 2 : 1;
+  d.hg = (int)(F / 512) / d.nch;
+  d.gs = (int)(G / d.gq);
+  return d;
+}
+
+inline int decode_target_wgs() {
+  static const int t = [] {
+    const char* e = std::getenv("RTKV_DECODE_WGS");  // tuning knob, default 1024 workgroups
+    const int v = e ? std::atoi(e) : 0;
+    return v > 0 ? v : 1024;
+  }();
+  return t;
+}
+
+// splits of `cap` rows (the packed rows' capacity, or the dense tail's)
+inline int decode_splits(int64_t B, int64_t G, int64_t F, int64_t cap) {
+  const DecodeShape d = decode_shape(F, G);
+  int64_t s = (cap + 16 * 4 - 1) / (16 * 4);    // at least ~16 rows per wave (kDW = 4 waves)
+  const int64_t wg = B * d.gs * (d.hg > 0 ? d.hg : 1);
+  const int64_t target = decode_target_wgs() / (wg > 0 ? wg : 1);
+  if (s > target) s = target;
+  if (s < 1) s = 1;
+  return (int)s;
+}
 
 
 constexpr int kDW = 4;  // waves per workgroup

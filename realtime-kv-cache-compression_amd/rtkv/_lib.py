@@ -72,6 +72,12 @@ class LayerOut(ctypes.Structure):
                 ("packed_capacity", c_i64), ("row_offset_dev", c_p), ("scale_zp_dev", c_p), ("stats_dev", c_p)]
 
 
+class DenseTail(ctypes.Structure):
+    """rtkv_dense_tail: the dense K/V rows of the tokens generated after the prefill."""
+    _fields_ = [("k_dev", c_p), ("v_dev", c_p), ("rows_dev", c_p), ("capacity", c_i64), ("stride_b", c_i64),
+                ("stride_s", c_i64)]
+
+
 class EarlyStats(ctypes.Structure):
     """rtkv_early_stats: the layer statistics the device publishes to host memory (B = 1) as one 128-byte
     line with the seq in its first and last word, then K4's final word ((seq mod 2^48) << 16 | flags)."""
@@ -169,6 +175,9 @@ _SIGS = {
     "rtkv_decode_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
     "rtkv_decode_attention_packed": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i32, c_p,
                                       c_p, c_i64, ctypes.c_float, c_p, c_p, c_sz, c_p], c_i32),
+    "rtkv_decode_tail_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
+    "rtkv_decode_attention_packed_tail": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64,
+                                           c_i32, c_p, c_p, c_i64, ctypes.c_float, c_p, c_p, c_p, c_sz, c_p], c_i32),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -4,6 +4,11 @@ north_star (reference src/models/compression_layers.py:7-45 and :96-175).
 CompressedKVCache keeps the reference's dict-of-tensors interface and adds the packed form of a layer
 (bit-packed integer codes + per-row scale/zero-point, as produced by rtkv_compress_layer) with an
 on-device decoder (rtkv_unpack_dequant) that reproduces the dequantized K'/V' bit for bit.
+
+Generation: the reference's decode steps do not compress; each appends the new token's dense K/V to
+the cache and attends over everything (modified_llama.py:83-94, 152).  DecodeTail holds those dense
+rows of one layer, and decode_attention(..., tail=...) attends over the packed rows followed by them
+(rtkv_decode_attention_packed_tail) without dequantizing the layer.
 """
 from __future__ import annotations
 
@@ -20,12 +25,14 @@ from .token_importance import _workspace
 class CompressedKVCache:
     """Per-layer storage of compressed K/V (compression_layers.py:7-45)."""
 
-    def __init__(self, max_batch_size: int, max_seq_len: int, head_dim: int):
+    def __init__(self, max_batch_size: int, max_seq_len: int, head_dim: int, tail_capacity: int = 256):
         self.max_batch_size = max_batch_size
         self.max_seq_len = max_seq_len
         self.head_dim = head_dim
+        self.tail_capacity = tail_capacity  # first allocation of a layer's DecodeTail (it doubles when full)
         self.cache_data: Dict[int, dict] = {}
         self.compression_info: Dict[int, dict] = {}
+        self.tails: Dict[int, "DecodeTail"] = {}
 
     def store_compressed_kv(self, layer_idx: int, keys: torch.Tensor, values: torch.Tensor,
                             importance_scores: torch.Tensor, precision_labels: torch.Tensor,
@@ -45,11 +52,13 @@ class CompressedKVCache:
     def clear_cache(self):
         self.cache_data.clear()
         self.compression_info.clear()
+        self.tails.clear()
 
     # ------------------------------------------------------------------ packed form (extension)
     def store_packed(self, layer_idx: int, packed: dict):
         """Keep only the packed codes of a layer (``info['packed']`` of compress_layer_kv_cache)."""
         self.compression_info[layer_idx] = packed
+        self.tails.pop(layer_idx, None)  # a new prefill: the tokens generated after the old one are gone
 
     def packed_nbytes(self, layer_idx: int) -> int:
         p = self.compression_info[layer_idx]
@@ -62,16 +71,127 @@ class CompressedKVCache:
         return unpack_layer(p)
 
     def attend(self, layer_idx: int, q: torch.Tensor, num_kv_heads: int, scale: Optional[float] = None):
-        """One decode step of attention over the packed layer (no dense K'/V'): fp32 [B, Hq, D]."""
-        return decode_attention(self.compression_info[layer_idx], q, num_kv_heads, scale)
+        """One decode step of attention over the packed layer (no dense K'/V'), followed by the
+        layer's appended tokens when there are any: fp32 [B, Hq, D]."""
+        return decode_attention(self.compression_info[layer_idx], q, num_kv_heads, scale,
+                                tail=self.tails.get(layer_idx))
+
+    def append(self, layer_idx: int, k_new: torch.Tensor, v_new: torch.Tensor):
+        """Append the dense K/V of newly generated tokens ([B, F] or [B, T, F], the layout
+        compress_layer_kv_cache takes) behind the layer's packed rows (modified_llama.py:83-94: a
+        decode step concatenates, it does not compress).  The layer's DecodeTail is created on first
+        use with the packed layer's dtype, feature_dim and batch size."""
+        t = self.tails.get(layer_idx)
+        if t is None:
+            p = self.compression_info[layer_idx]
+            t = self.tails[layer_idx] = DecodeTail(p["kept_index"].shape[0], int(p["feature_dim"]), p["dtype"],
+                                                   p["codes_k"].device, capacity=self.tail_capacity)
+        t.append(k_new, v_new)
+
+    def tail_len(self, layer_idx: int) -> int:
+        """Tokens appended to the layer since its packed rows were stored."""
+        t = self.tails.get(layer_idx)
+        return 0 if t is None else len(t)
 
     def save(self, path: str):
-        """Write every packed layer to one safetensors file (see save_packed for the format)."""
+        """Write every packed layer to one safetensors file (see save_packed for the format).
+        Appended tokens (the DecodeTails) are not serialized: the file holds the prefill only."""
         save_packed(self.compression_info, path)
 
     def load(self, path: str, device="cuda"):
-        """Read the packed layers of a file written by save(); replaces the packed layers held."""
+        """Read the packed layers of a file written by save(); replaces the packed layers held and
+        drops every tail (the file has none)."""
         self.compression_info = load_packed(path, device)
+        self.tails.clear()
+
+
+class DecodeTail:
+    """The dense K/V rows of the tokens generated after the prefill, for one layer: k, v
+    [B, capacity, F] in the K/V dtype and rows_dev (int64 [B], rows in use), all on one device.
+    append() copies with torch ops and advances rows_dev on the device — no host→device copy per
+    step — and doubles the buffers when they are full.  Not serialized with the packed layers."""
+
+    def __init__(self, B: int, feature_dim: int, dtype: torch.dtype, device, capacity: int = 256):
+        if dtype not in L.TORCH_DTYPE_CODE:
+            raise ValueError(f"DecodeTail: unsupported dtype {dtype} (float32, float16, bfloat16)")
+        if B < 1 or feature_dim < 1 or capacity < 1:
+            raise ValueError("DecodeTail: B, feature_dim and capacity must be positive")
+        if (feature_dim * torch.empty(0, dtype=dtype).element_size()) % 16:
+            raise ValueError("DecodeTail: rows must be a multiple of 16 bytes")
+        self.k = torch.zeros(B, capacity, feature_dim, dtype=dtype, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.rows_dev = torch.zeros(B, dtype=torch.int64, device=device)
+        self._len: Optional[int] = 0  # rows appended (the same for every batch row); None: caller-owned
+
+    @classmethod
+    def from_tensors(cls, k: torch.Tensor, v: torch.Tensor, rows: torch.Tensor) -> "DecodeTail":
+        """Wrap caller-owned buffers k, v [B, capacity, F] (same dtype, device and strides, unit
+        stride along F, batch and row strides and the base 16-byte aligned) with per-row counts
+        `rows` (int64 [B]) that may differ.  Counts are checked against [0, capacity] when `rows`
+        is on the host (it is then copied to the buffers' device once); on the device the kernel
+        clamps them.  Such a tail cannot be appended to."""
+        if k.dim() != 3 or v.shape != k.shape:
+            raise ValueError("DecodeTail: k and v must both be [B, capacity, F]")
+        if k.dtype not in L.TORCH_DTYPE_CODE or v.dtype != k.dtype:
+            raise ValueError(f"DecodeTail: k and v must share one of float32/float16/bfloat16 (got {k.dtype}, {v.dtype})")
+        if v.device != k.device:
+            raise ValueError("DecodeTail: k and v are on different devices")
+        B, cap, F = k.shape
+        if rows.dtype != torch.int64 or rows.shape != (B,):
+            raise ValueError(f"DecodeTail: rows must be int64 [{B}], got {rows.dtype} {tuple(rows.shape)}")
+        e = k.element_size()
+        if cap > 0 and B * F > 0:
+            if k.stride() != v.stride() or k.stride(2) != 1 or k.stride(1) < F:
+                raise ValueError("DecodeTail: k and v need the same strides, unit stride along F and stride_s >= F")
+            if (k.stride(0) * e) % 16 or (k.stride(1) * e) % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+                raise ValueError("DecodeTail: base pointers, stride_b and stride_s must keep rows 16-byte aligned")
+        if not rows.is_cuda:
+            if any(int(r) < 0 or int(r) > cap for r in rows.tolist()):
+                raise ValueError(f"DecodeTail: row counts {rows.tolist()} outside [0, {cap}]")
+            rows = rows.to(k.device)
+        elif rows.device != k.device:
+            raise ValueError("DecodeTail: rows is on another device than k and v")
+        t = cls.__new__(cls)
+        t.k, t.v, t.rows_dev, t._len = k, v, rows.contiguous(), None
+        return t
+
+    @property
+    def capacity(self) -> int:
+        return self.k.shape[1]
+
+    def __len__(self) -> int:
+        if self._len is None:
+            raise TypeError("DecodeTail.from_tensors: the row counts live in rows_dev")
+        return self._len
+
+    def append(self, k_new: torch.Tensor, v_new: torch.Tensor):
+        """k_new, v_new: [B, F] or [B, T, F] (T >= 1), the layout compress_layer_kv_cache takes."""
+        if self._len is None:
+            raise ValueError("DecodeTail.from_tensors wraps caller-owned buffers: append to them directly")
+        if k_new.dim() == 2:
+            k_new, v_new = k_new.unsqueeze(1), v_new.unsqueeze(1) if v_new.dim() == 2 else v_new
+        B, cap, F = self.k.shape
+        if k_new.dim() != 3 or v_new.shape != k_new.shape or k_new.shape[0] != B or k_new.shape[2] != F \
+                or k_new.shape[1] < 1:
+            raise ValueError(f"DecodeTail.append: expected [{B}, {F}] or [{B}, T, {F}], got {tuple(k_new.shape)} / "
+                             f"{tuple(v_new.shape)}")
+        if k_new.dtype != self.k.dtype or v_new.dtype != self.k.dtype:
+            raise ValueError(f"DecodeTail.append: dtype {k_new.dtype} / {v_new.dtype}, the tail holds {self.k.dtype}")
+        if k_new.device != self.k.device or v_new.device != self.k.device:
+            raise ValueError(f"DecodeTail.append: tensors on {k_new.device}, the tail is on {self.k.device}")
+        T, n = k_new.shape[1], self._len
+        if n + T > cap:
+            while cap < n + T:
+                cap *= 2
+            for name in ("k", "v"):
+                old = getattr(self, name)
+                new = torch.zeros(B, cap, F, dtype=old.dtype, device=old.device)
+                new[:, :n] = old[:, :n]
+                setattr(self, name, new)
+        self.k[:, n:n + T] = k_new
+        self.v[:, n:n + T] = v_new
+        self.rows_dev += T
+        self._len = n + T
 
 
 # ---------------------------------------------------------------------- packed (de)serialization
@@ -199,13 +319,18 @@ def unpack_layer(p: dict):
     return outs[0], outs[1]
 
 
-def decode_attention(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optional[float] = None) -> torch.Tensor:
+def decode_attention(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optional[float] = None,
+                     tail: Optional[DecodeTail] = None) -> torch.Tensor:
     """Attention of one new token per batch row over a packed layer, decoded on the fly
     (rtkv_decode_attention_packed).  q: [B, Hq, D] in the layer's dtype; returns fp32 [B, Hq, D] =
     softmax(q·K'ᵀ·scale)·V' over the kept rows, with K'/V' exactly the dequantized rows
     (modified_llama.py:140-142 attends over those dequantized floats).  scale defaults to 1/sqrt(D)
-    (modified_llama.py:89)."""
+    (modified_llama.py:89).  tail: the dense rows of the tokens generated since (DecodeTail); the
+    softmax then runs over the kept rows followed by the tail's rows, what a decode step of the
+    reference attends over (modified_llama.py:83-94, 152; rtkv_decode_attention_packed_tail)."""
     codes_k, codes_v = p["codes_k"], p["codes_v"]
+    if tail is not None:
+        return _decode_attention_tail(p, q, num_kv_heads, scale, tail)
     L.require_device(codes_k, codes_v, q)
     dev = codes_k.device
     if q.dtype != p["dtype"]:
@@ -248,6 +373,59 @@ def decode_attention(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optiona
                                                  Sp, rows.data_ptr(), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype],
                                                  bits, qc.data_ptr(), Hq, sc, out.data_ptr(), ws.data_ptr(),
                                                  ws.numel(), L.stream_ptr(dev)), "rtkv_decode_attention_packed")
+    return out
+
+
+def _decode_attention_tail(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optional[float], tail: DecodeTail):
+    codes_k, codes_v = p["codes_k"], p["codes_v"]
+    L.require_device(codes_k, codes_v, q, tail.k, tail.v, tail.rows_dev)
+    dev = q.device
+    if q.dtype != p["dtype"]:
+        raise ValueError(f"q dtype {q.dtype} does not match the packed layer's {p['dtype']}")
+    B, Hq, D = q.shape
+    F = int(p["feature_dim"])
+    if num_kv_heads * D != F:
+        raise ValueError(f"num_kv_heads * head_dim = {num_kv_heads * D} != feature_dim {F}")
+    if tail.k.dtype != q.dtype or tail.k.shape[0] != B or tail.k.shape[2] != F or tail.k.device != dev \
+            or tail.v.shape != tail.k.shape or tail.rows_dev.shape != (B,) or tail.rows_dev.dtype != torch.int64:
+        raise ValueError(f"tail [{tuple(tail.k.shape)} {tail.k.dtype}] does not match q's batch {B}, feature_dim {F}, "
+                         f"dtype {q.dtype}")
+    row_offset = p["row_offset"].contiguous()
+    scale_zp = p["scale_zp"].contiguous()
+    kept_index = p["kept_index"].contiguous()
+    labels = p["labels"].contiguous()
+    _check_dtypes("decode", p)
+    if kept_index.dim() != 2 or kept_index.shape[0] != B or len(p["rows"]) != B or labels.shape[0] != B \
+            or row_offset.shape[0] != B or scale_zp.shape[0] != B:
+        raise ValueError(f"q has {B} batch rows but the packed layer has {kept_index.shape[0]} "
+                         f"(rows {len(p['rows'])}, labels {labels.shape[0]})")
+    Sp = kept_index.shape[1]
+    if row_offset.shape != (B, Sp) or scale_zp.shape != (B, Sp, 4):
+        raise ValueError("packed layer: row_offset / scale_zp shapes disagree with kept_index")
+    if codes_k.numel() != codes_v.numel():
+        raise ValueError("codes_k and codes_v differ in size")
+    if any(int(r) < 0 or int(r) > Sp for r in p["rows"]):
+        raise ValueError(f"row counts {p['rows']} outside [0, {Sp}]")
+    S = labels.shape[1]
+    rows = p.get("_rows_dev")
+    if rows is None or rows.device != dev:
+        rows = p["_rows_dev"] = torch.tensor(p["rows"], dtype=torch.int64, device=dev)
+    out = torch.zeros(B, Hq, D, dtype=torch.float32, device=dev)
+    bits = (ctypes.c_int32 * 3)(*p["bits"])
+    qc = q.contiguous()
+    cap = tail.capacity
+    dt = L.DenseTail(L.ptr(tail.k) if cap else 0, L.ptr(tail.v) if cap else 0, tail.rows_dev.data_ptr(), cap,
+                     tail.k.stride(0), tail.k.stride(1))
+    ws = torch.empty(L.lib().rtkv_decode_tail_workspace_size(B, Hq, num_kv_heads, D, Sp, cap), dtype=torch.uint8,
+                     device=dev)
+    sc = float(scale) if scale is not None else 1.0 / float(D) ** 0.5
+    pk = (lambda t: t.data_ptr()) if Sp else (lambda t: 0)  # no packed row capacity: null packed pointers
+    L.check(L.lib().rtkv_decode_attention_packed_tail(pk(codes_k), pk(codes_v), codes_k.numel(), pk(row_offset),
+                                                      pk(scale_zp), pk(kept_index), pk(labels), B, S, Sp,
+                                                      pk(rows), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype], bits,
+                                                      qc.data_ptr(), Hq, sc, ctypes.byref(dt), out.data_ptr(),
+                                                      ws.data_ptr(), ws.numel(), L.stream_ptr(dev)),
+            "rtkv_decode_attention_packed_tail")
     return out
 
 

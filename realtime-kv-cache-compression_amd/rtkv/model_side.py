@@ -140,6 +140,39 @@ class CompressedPrefillAttention:
         return out, (ck, cv), info
 
 
+class CompressedDecodeAttention:
+    """The decode step (q_len == 1) of CompressedLlamaAttention over a CompressedKVCache whose layer
+    holds the prefill's packed rows (store_packed): the reference does not compress here, it
+    concatenates the new token's K/V onto the cache and attends over all of it
+    (modified_llama.py:83-94), then lays the output out as [B, 1, hidden] (:152-156).  The packed
+    rows are decoded in the kernel and the tokens generated so far stay dense in the layer's
+    DecodeTail (rtkv_decode_attention_packed_tail): nothing is dequantized to memory."""
+
+    def __init__(self, cache, num_heads: int, num_kv_heads: int, head_dim: int, layer_idx: int):
+        self.cache = cache
+        self.num_heads = num_heads
+        self.num_kv_heads = num_kv_heads
+        self.head_dim = head_dim
+        self.layer_idx = layer_idx
+
+    def __call__(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
+                 attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """query [B,Hq,1,D], key/value [B,Hkv,1,D] (post-RoPE) → attn_output [B, 1, Hq·D] before
+        o_proj, in the query dtype.  Appends the token to the layer's tail, then attends over the
+        packed rows and the tail, the new token's own row included."""
+        if attention_mask is not None:
+            raise ValueError("CompressedDecodeAttention takes no decode-step attention mask")
+        B, H, Q, D = query_states.shape
+        Hkv = key_states.shape[1]
+        if H != self.num_heads or Hkv != self.num_kv_heads or D != self.head_dim or Q != 1 \
+                or key_states.shape != (B, Hkv, 1, D) or value_states.shape != key_states.shape:
+            raise ValueError("state shapes do not match the layer's head configuration with q_len == 1")
+        self.cache.append(self.layer_idx, key_states.transpose(1, 2).reshape(B, 1, Hkv * D),
+                          value_states.transpose(1, 2).reshape(B, 1, Hkv * D))
+        out = self.cache.attend(self.layer_idx, query_states[:, :, 0, :], Hkv)
+        return out.to(query_states.dtype).reshape(B, 1, H * D)
+
+
 def split_attention_mask(attention_mask: torch.Tensor, B: int, S: int):
     """The model's additive mask [B or 1, 1, S, >=S] → (key_bias, valid_key): None, None for the plain
     causal mask; else the fp32 [B, S] key bias (0 real key, -inf padding key) and the bool [B, S]

@@ -1,0 +1,323 @@
+"""GPU: one decode step of attention over a packed layer followed by a dense tail of new tokens
+(rtkv_decode_attention_packed_tail, decode_tail.hip) against a plain PyTorch fp32 reference over
+cat(K'[:rows[b]], tail[:tail_rows[b]]) per batch row.
+
+A decode step of the reference model does not compress: it concatenates the new token's K/V onto the
+cache and attends over all of it (modified_llama.py:83-94, 152).  The kernel reads the packed rows
+as rtkv_decode_attention_packed does and the tail rows as stored, one softmax over both.  The error
+sources are those of tests/test_gpu_decode.py — fp32 summation order and the hardware exp2 — so the
+tolerance is that file's: rtol = 2e-4, atol = 2e-5 · max(max|V'|, max|tail V|, 1).
+
+Every unused tail row (capacity is always above the count) is filled with NaN: a finite output
+within tolerance shows that nothing at or past the count is read."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import synth
+
+pytestmark = pytest.mark.gpu
+
+TD = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
+COV = dict(alpha=0.8, beta=0.1, gamma=0.1, theta_h=0.4, theta_m=0.25)
+TAILS = (1, 3, 5, 257, 1500)   # one row; fewer than the 4 waves; 5; past one 64-row round; several tail splits
+
+
+@pytest.fixture(scope="module", autouse=True)
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no ROCm device")
+    import rtkv
+    rtkv.build()
+
+
+def dev(stored: np.ndarray, dtype: str) -> torch.Tensor:
+    if dtype == "float32":
+        return torch.from_numpy(np.ascontiguousarray(stored, np.float32)).cuda()
+    return torch.from_numpy(np.ascontiguousarray(stored, np.uint16).view(np.int16)).cuda().view(TD[dtype])
+
+
+def rand(seed, shape, dtype, mul=1.0):
+    return dev(synth.cast(synth.normal(seed, shape) * np.float32(mul), dtype), dtype)
+
+
+_LAYERS = {}
+
+
+def layer(B, S, Hkv, D, dtype, bits=(2, 4, 8), ratio=0.6):
+    """(K', V', packed) of one compressed synthetic layer, computed once per shape and left unchanged."""
+    key = (B, S, Hkv, D, dtype, bits, ratio)
+    if key not in _LAYERS:
+        import rtkv
+        F = Hkv * D
+        seed = S * 7 + Hkv
+        K, V = synth.kv(seed, B, S, F, dtype)
+        W = synth.attention_slice(seed, B, 8, S, rtkv.prompt_length(S), dtype)
+        cfg = rtkv.CompressionConfig(num_hidden_layers=4, low_precision_bits=bits[0], medium_precision_bits=bits[1],
+                                     high_precision_bits=bits[2], early_layer_ratio=ratio, middle_layer_ratio=ratio,
+                                     later_layer_ratio=ratio, **COV)
+        comp = rtkv.RealTimePrefillCompressor(cfg)
+        ids = torch.zeros(B, S, dtype=torch.long, device="cuda")
+        k2, v2, info = comp.compress_layer_kv_cache(dev(K, dtype), dev(V, dtype), dev(W, dtype), ids, 1)
+        _LAYERS[key] = (k2, v2, info["packed"])
+    return _LAYERS[key]
+
+
+def reference(k2, v2, rows, tk, tv, trows, q, Hkv, scale):
+    """softmax(q·Xᵀ·scale)·Y in fp32 per batch row, X/Y = cat(K'/V'[:rows[b]], tail[:trows[b]])."""
+    B, Hq, D = q.shape
+    G = Hq // Hkv
+    out = torch.zeros(B, Hq, D, dtype=torch.float32, device=q.device)
+    for b in range(B):
+        n, t = int(rows[b]), int(trows[b])
+        if n + t == 0:
+            continue
+        Kf = torch.cat([k2[b, :n].float(), tk[b, :t].float()]).view(n + t, Hkv, D)
+        Vf = torch.cat([v2[b, :n].float(), tv[b, :t].float()]).view(n + t, Hkv, D)
+        qf = q[b].float().view(Hkv, G, D)
+        s = torch.einsum("hgd,nhd->hgn", qf, Kf) * scale
+        p = torch.softmax(s, dim=-1)
+        out[b] = torch.einsum("hgn,nhd->hgd", p, Vf).reshape(Hq, D)
+    return out
+
+
+def make_tail(seed, B, T, F, dtype, spare=3, kmul=1.0):
+    """Dense tail buffers [B, T + spare, F] with T rows in use and NaN in every unused row."""
+    tk = rand(seed, (B, T + spare, F), dtype, kmul)
+    tv = rand(seed + 1, (B, T + spare, F), dtype)
+    tk[:, T:] = float("nan")
+    tv[:, T:] = float("nan")
+    return tk, tv
+
+
+def check(out, ref, v2, tv, trows):
+    assert torch.isfinite(out).all()
+    tmax = max([tv[b, :int(t)].float().abs().max().item() for b, t in enumerate(trows) if int(t)] + [0.0])
+    vmax = max(v2.float().abs().max().item() if v2.numel() else 0.0, tmax, 1.0)
+    torch.testing.assert_close(out, ref, rtol=2e-4, atol=2e-5 * vmax)
+
+
+SHAPES = [
+    # S, Hkv, D, Hq            lane shape (chunks per lane, query heads per lane)
+    (700, 4, 128, 4),        # F = 512, G = 1: 1 chunk, 1 head
+    (900, 8, 128, 8),        # F = 1024, G = 1: 2 chunks
+    (620, 4, 128, 8),        # G = 2: 2 heads
+    (1000, 4, 128, 16),      # G = 4: 4 heads
+    (800, 8, 64, 8),         # head_dim 64: lanes per head at run time
+    (650, 2, 256, 16),       # head_dim 256, G = 8: 4 heads × 2 query-head groups
+]
+CASES = [(s, dt, (2, 4, 8)) for s in SHAPES[:3] for dt in ("float16", "bfloat16", "float32")] \
+    + [(s, "float32", (4, 8, 16)) for s in SHAPES[:3]] \
+    + [(s, "float16", (2, 4, 8)) for s in SHAPES[3:]]
+
+
+@pytest.mark.parametrize("shape,dtype,bits", CASES, ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_packed_rows_then_tail(shape, dtype, bits):
+    import rtkv
+    S, Hkv, D, Hq = shape
+    F = Hkv * D
+    k2, v2, pk = layer(1, S, Hkv, D, dtype, bits)
+    q = rand(S + 1, (1, Hq, D), dtype)
+    for T in TAILS:
+        tk, tv = make_tail(S + 10 * T, 1, T, F, dtype)
+        tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([T]))
+        out = rtkv.decode_attention(pk, q, Hkv, tail=tail)
+        ref = reference(k2, v2, pk["rows"], tk, tv, [T], q, Hkv, 1.0 / D ** 0.5)
+        check(out, ref, v2, tv, [T])
+        assert torch.equal(rtkv.decode_attention(pk, q, Hkv, tail=tail), out)   # deterministic
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16", "float32"])
+def test_empty_tail_has_the_no_tail_bits(dtype):
+    import rtkv
+    S, Hkv, D, Hq = 900, 8, 128, 8
+    k2, v2, pk = layer(1, S, Hkv, D, dtype)
+    q = rand(5, (1, Hq, D), dtype)
+    plain = rtkv.decode_attention(pk, q, Hkv)
+    tk, tv = make_tail(6, 1, 0, Hkv * D, dtype, spare=8)
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.zeros(1, dtype=torch.int64, device="cuda"))
+    assert torch.equal(rtkv.decode_attention(pk, q, Hkv, tail=tail), plain)
+    # existing callers still reach the old entry point: no append, no tail
+    cache = rtkv.CompressedKVCache(1, S, D)
+    cache.store_packed(0, pk)
+    assert cache.tail_len(0) == 0 and torch.equal(cache.attend(0, q, Hkv), plain)
+    # a freshly allocated tail (no token yet) changes nothing either
+    assert torch.equal(rtkv.decode_attention(pk, q, Hkv, tail=rtkv.DecodeTail(1, Hkv * D, TD[dtype], "cuda", 4)), plain)
+
+
+def test_batch_of_two_with_strided_tail():
+    """Different kept counts per row, tail_rows = [0, 7], a batch stride larger than capacity · F."""
+    import rtkv
+    B, S, Hkv, D, Hq, dtype = 2, 800, 8, 128, 32, "float16"
+    F = Hkv * D
+    k2, v2, pk0 = layer(B, S, Hkv, D, dtype, ratio=0.5)
+    pk = {k: v for k, v in pk0.items() if k != "_rows_dev"}
+    pk["rows"] = [int(pk0["rows"][0]), int(pk0["rows"][1]) - 17]   # the first rows of row 1's kept list
+    cap = 9
+    big_k, big_v = make_tail(21, B, 0, F, dtype, spare=cap + 4)    # NaN everywhere
+    tk, tv = big_k[:, :cap], big_v[:, :cap]
+    tk[1, :7] = rand(22, (7, F), dtype)
+    tv[1, :7] = rand(23, (7, F), dtype)
+    assert tk.stride(0) > cap * F
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([0, 7]))
+    q = rand(24, (B, Hq, D), dtype)
+    out = rtkv.decode_attention(pk, q, Hkv, tail=tail)
+    ref = reference(k2, v2, pk["rows"], tk, tv, [0, 7], q, Hkv, 1.0 / D ** 0.5)
+    check(out, ref, v2, tv, [0, 7])
+    # row 0 has no tail row: the bits of the packed-only step
+    assert torch.equal(out[0], rtkv.decode_attention(pk, q, Hkv)[0])
+
+
+def empty_packed(B, F, dtype):
+    z = lambda *s, dt: torch.zeros(*s, dtype=dt, device="cuda")  # noqa: E731
+    return {"codes_k": z(0, dt=torch.uint8), "codes_v": z(0, dt=torch.uint8), "row_offset": z(B, 0, dt=torch.int64),
+            "scale_zp": z(B, 0, 4, dt=torch.float32), "kept_index": z(B, 0, dt=torch.int32),
+            "labels": z(B, 8, dt=torch.uint8), "rows": [0] * B, "bits": (2, 4, 8), "dtype": TD[dtype], "feature_dim": F}
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16", "float32"])
+def test_tail_only(dtype):
+    """No packed row (rows = [0]) and no packed capacity at all (S' == 0 tensors): attention over
+    the tail alone; neither with a tail row: zeros."""
+    import rtkv
+    S, Hkv, D, Hq = 620, 4, 128, 8
+    F = Hkv * D
+    k2, v2, pk0 = layer(1, S, Hkv, D, dtype)
+    none = {k: v for k, v in pk0.items() if k != "_rows_dev"}
+    none["rows"] = [0]
+    q = rand(31, (1, Hq, D), dtype)
+    for T in (1, 70):
+        tk, tv = make_tail(32 + T, 1, T, F, dtype)
+        tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([T]))
+        ref = reference(k2[:, :0], v2[:, :0], [0], tk, tv, [T], q, Hkv, 1.0 / D ** 0.5)
+        for p in (none, empty_packed(1, F, dtype)):
+            check(rtkv.decode_attention(p, q, Hkv, tail=tail), ref, v2[:, :0], tv, [T])
+    tk, tv = make_tail(40, 1, 0, F, dtype, spare=5)
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([0]))
+    for p in (none, empty_packed(1, F, dtype)):
+        assert torch.count_nonzero(rtkv.decode_attention(p, q, Hkv, tail=tail)) == 0
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16", "float32"])
+def test_dominance_both_ways(dtype):
+    """The running maximum across the packed/tail merge.  A tail key equal to q for one query head
+    (|q|²/√D ≈ 16·√D, far above q·k of any other row) puts that head's whole weight on its tail row;
+    a tail of tiny keys (scores ≈ 0, below the packed rows' maximum) only mixes in per the reference."""
+    import rtkv
+    S, Hkv, D, Hq = 620, 4, 128, 8
+    F, G = Hkv * D, Hq // Hkv
+    k2, v2, pk = layer(1, S, Hkv, D, dtype)
+    q = rand(41, (1, Hq, D), dtype, mul=4.0)
+    T, t_hit, hq = 5, 3, 5
+    tk, tv = make_tail(42, 1, T, F, dtype)
+    h = hq // G
+    tk[0, t_hit, h * D:(h + 1) * D] = q[0, hq]
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([T]))
+    out = rtkv.decode_attention(pk, q, Hkv, tail=tail)
+    ref = reference(k2, v2, pk["rows"], tk, tv, [T], q, Hkv, 1.0 / D ** 0.5)
+    check(out, ref, v2, tv, [T])
+    vmax = max(v2.float().abs().max().item(), tv[:, :T].float().abs().max().item(), 1.0)
+    torch.testing.assert_close(out[0, hq], tv[0, t_hit, h * D:(h + 1) * D].float(), rtol=2e-4, atol=2e-5 * vmax)
+    # the other way: tiny tail keys
+    tk, tv = make_tail(44, 1, 70, F, dtype, kmul=1e-3)
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([70]))
+    out = rtkv.decode_attention(pk, q, Hkv, tail=tail)
+    ref = reference(k2, v2, pk["rows"], tk, tv, [70], q, Hkv, 1.0 / D ** 0.5)
+    check(out, ref, v2, tv, [70])
+
+
+def test_count_above_capacity_is_clamped():
+    import rtkv
+    S, Hkv, D, Hq, dtype = 700, 4, 128, 4, "float16"
+    k2, v2, pk = layer(1, S, Hkv, D, dtype)
+    cap = 6
+    tk, tv = make_tail(51, 1, cap, Hkv * D, dtype, spare=0)
+    q = rand(52, (1, Hq, D), dtype)
+    full = rtkv.decode_attention(pk, q, Hkv, tail=rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([cap])))
+    over = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([cap + 1000], device="cuda"))
+    assert torch.equal(rtkv.decode_attention(pk, q, Hkv, tail=over), full)
+    neg = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([-3], device="cuda"))
+    assert torch.equal(rtkv.decode_attention(pk, q, Hkv, tail=neg), rtkv.decode_attention(pk, q, Hkv))
+
+
+def test_rejected_input():
+    import rtkv
+    import rtkv._lib as L
+    S, Hkv, D, Hq, dtype = 700, 4, 128, 4, "float16"
+    F = Hkv * D
+    k2, v2, pk = layer(1, S, Hkv, D, dtype)
+    q = rand(61, (1, Hq, D), dtype)
+    tk, tv = make_tail(62, 1, 2, F, dtype)
+    good = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([2]))
+    with pytest.raises(ValueError):
+        rtkv.decode_attention(pk, q.float(), Hkv, tail=good)                     # q of another dtype
+    with pytest.raises(ValueError):
+        rtkv.decode_attention(pk, q, Hkv, tail=rtkv.DecodeTail(1, F, torch.bfloat16, "cuda", 4))
+    wide = rand(63, (1, 5, F + 4), dtype)
+    with pytest.raises(ValueError):
+        rtkv.DecodeTail.from_tensors(wide[:, :, :F], wide[:, :, :F], torch.tensor([2]))   # misaligned rows
+    # the same buffers handed to the library without the Python check: refused there, nothing launched
+    raw = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([2]))
+    raw.k = raw.v = wide[:, :, :F]
+    with pytest.raises(RuntimeError, match="decode"):
+        rtkv.decode_attention(pk, q, Hkv, tail=raw)
+    raw.k = raw.v = wide.reshape(-1)[4:4 + 5 * F].view(1, 5, F)                  # base 8 bytes off
+    with pytest.raises(RuntimeError, match="decode"):
+        rtkv.decode_attention(pk, q, Hkv, tail=raw)
+    # the C ABI's own argument checks (tail-only call: the packed pointers may be null)
+    out = torch.zeros(1, Hq, D, device="cuda")
+    ws_bytes = L.lib().rtkv_decode_tail_workspace_size(1, Hq, Hkv, D, 0, 5)
+    assert ws_bytes > 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    rows_dev = torch.tensor([2], device="cuda")
+
+    def call(t, nbytes):
+        return L.lib().rtkv_decode_attention_packed_tail(0, 0, 0, 0, 0, 0, 0, 1, 1, 0, 0, Hkv, D, L.F16, None,
+                                                         q.data_ptr(), Hq, 0.1, ctypes.byref(t), out.data_ptr(),
+                                                         ws.data_ptr(), nbytes, L.stream_ptr(q.device))
+    ok = L.DenseTail(tk.data_ptr(), tv.data_ptr(), rows_dev.data_ptr(), 5, tk.stride(0), tk.stride(1))
+    assert call(ok, ws_bytes) == 0
+    for bad, nbytes in ((L.DenseTail(tk.data_ptr(), tv.data_ptr(), rows_dev.data_ptr(), -1, tk.stride(0), F), ws_bytes),
+                        (L.DenseTail(tk.data_ptr(), tv.data_ptr(), 0, 5, tk.stride(0), F), ws_bytes),
+                        (L.DenseTail(tk.data_ptr(), tv.data_ptr(), rows_dev.data_ptr(), 5, tk.stride(0), F + 4), ws_bytes),
+                        (ok, ws_bytes - 1024)):
+        assert call(bad, nbytes) == -1                                           # RTKV_ERR_INVALID
+        assert "decode: " in L.lib().rtkv_last_error().decode()
+    torch.cuda.synchronize()
+
+
+def test_generation_loop():
+    """store_packed, then 6 decode steps through CompressedDecodeAttention with a tail that starts
+    at 4 rows and grows mid-loop; each step against torch over cat(K', tokens so far)."""
+    import rtkv
+    B, S, Hkv, D, Hq, dtype = 1, 512, 8, 128, 32, "float16"
+    F = Hkv * D
+    k2, v2, pk = layer(B, S, Hkv, D, dtype)
+    cache = rtkv.CompressedKVCache(B, S, D, tail_capacity=4)
+    cache.store_packed(2, pk)
+    att = rtkv.CompressedDecodeAttention(cache, Hq, Hkv, D, 2)
+    ks, vs = [], []
+    for step in range(6):
+        q = rand(70 + step, (B, Hq, 1, D), dtype)
+        k = rand(80 + step, (B, Hkv, 1, D), dtype)
+        v = rand(90 + step, (B, Hkv, 1, D), dtype)
+        out = att(q, k, v)
+        assert out.shape == (B, 1, Hq * D) and out.dtype == TD[dtype]
+        assert cache.tail_len(2) == step + 1
+        ks.append(k.transpose(1, 2).reshape(B, 1, F))
+        vs.append(v.transpose(1, 2).reshape(B, 1, F))
+        tk, tv = torch.cat(ks, 1), torch.cat(vs, 1)
+        ref = reference(k2, v2, pk["rows"], tk, tv, [step + 1], q[:, :, 0], Hkv, 1.0 / D ** 0.5)
+        # the module returns the fp32 result rounded to the query dtype
+        vmax = max(v2.float().abs().max().item(), tv.float().abs().max().item(), 1.0)
+        full = cache.attend(2, q[:, :, 0], Hkv)
+        torch.testing.assert_close(full, ref, rtol=2e-4, atol=2e-5 * vmax)
+        assert torch.equal(out, full.to(TD[dtype]).reshape(B, 1, Hq * D))
+    assert cache.tails[2].capacity == 8
+    with pytest.raises(ValueError):
+        att(q, k, v, attention_mask=torch.zeros(B, 1, 1, 1, device="cuda"))
+    cache.store_packed(2, pk)
+    assert cache.tail_len(2) == 0
+    assert torch.equal(cache.attend(2, q[:, :, 0], Hkv), rtkv.decode_attention(pk, q[:, :, 0], Hkv))

@@ -2,7 +2,14 @@
 (rtkv_decode_attention_packed) against torch SDPA over the dense dequantized K'/V' the reference
 keeps (modified_llama.py:140-142), on a cfg3-shaped layer (B = 1, S = 16384, Hkv = 32, D = 128 f16,
 ratio 0.6, bits 2/4/8) and Llama-3-8B-shaped GQA (Hkv = 8).  Prints µs per step and the algorithmic
-HBM bytes / time (packed codes + per-row scale/zp + kept_index / row_offset + labels gather)."""
+HBM bytes / time (packed codes + per-row scale/zp + kept_index / row_offset + labels gather).
+
+--tail T[,T...]: after each no-tail line, the step over the packed rows followed by a dense tail of T
+generated tokens (rtkv_decode_attention_packed_tail) next to dense SDPA over cat(K', tail), with the
+rate of the added bytes 2·T·F·e / (t_T − t_0), t_0 the no-tail step.
+
+usage: decode_bench.py [cases e.g. 0,2] [iters] [--tail 0,128,1024,4096]"""
+import argparse
 import os
 import sys
 import time
@@ -24,7 +31,41 @@ def dev(stored, dtype):
     return torch.from_numpy(np.ascontiguousarray(stored, np.uint16).view(np.int16)).cuda().view(TD[dtype])
 
 
-def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200):
+def timed(fn, iters):
+    """µs per call: device events around `iters` calls after 10 warm-up calls."""
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def run_tails(pk, k2, v2, n, q, Hkv, Hq, D, us0, tails, iters):
+    """The step with a dense tail of T rows, for each T, against SDPA over cat(K', tail)."""
+    F, e = Hkv * D, q.element_size()
+    for T in tails:
+        tail = rtkv.DecodeTail(1, F, q.dtype, "cuda", capacity=max(T, 1))
+        if T:
+            tail.append(torch.randn(1, T, F, device="cuda").to(q.dtype), torch.randn(1, T, F, device="cuda").to(q.dtype))
+        us = timed(lambda: rtkv.decode_attention(pk, q, Hkv, tail=tail), iters)
+        kd = torch.cat([k2[:, :n], tail.k[:, :T]], 1).view(1, n + T, Hkv, D).transpose(1, 2)
+        vd = torch.cat([v2[:, :n], tail.v[:, :T]], 1).view(1, n + T, Hkv, D).transpose(1, 2)
+        kd = kd.repeat_interleave(Hq // Hkv, 1).contiguous()
+        vd = vd.repeat_interleave(Hq // Hkv, 1).contiguous()
+        qq = q.view(1, Hq, 1, D)
+        us_d = timed(lambda: torch.nn.functional.scaled_dot_product_attention(qq, kd, vd), iters)
+        added = 2 * T * F * e
+        rate = f"{added / (us - us0) / 1e3:.0f} GB/s" if T and us > us0 else "n/a"
+        print(f"    tail T={T}: decode {us:.1f} us (no tail {us0:.1f} us; +{added/1e6:.2f} MB dense tail at {rate}) | "
+              f"dense SDPA over cat(K', tail) {us_d:.1f} us", flush=True)
+
+
+def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200, tails=()):
     F = Hkv * D
     K, V = synth.kv(11, 1, S, F, dtype)
     W = synth.attention_slice(11, 1, 8, S, rtkv.prompt_length(S), dtype)
@@ -69,13 +110,20 @@ def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200):
     print(f"S={S} Hkv={Hkv} Hq={Hq} {dtype}: kept {n}, packed {code_bytes/1e6:.2f} MB ({code_bytes*8/(2*n*F):.2f} bits/elem) "
           f"-> decode {us:.1f} us, {by/us/1e3:.0f} GB/s algorithmic | dense SDPA over K'/V' {us_d:.1f} us "
           f"({dense_by/1e6:.1f} MB, {dense_by/us_d/1e3:.0f} GB/s)", flush=True)
+    if tails:
+        run_tails(pk, k2, v2, n, q, Hkv, Hq, D, us, tails, iters)
 
 
 if __name__ == "__main__":
     rtkv.build()
     cases = ((16384, 32, 32), (32768, 32, 32), (16384, 8, 32), (131072, 8, 32), (131072, 8, 8), (32768, 32, 128),
              (32768, 32, 32, "bfloat16"), (131072, 8, 32, "bfloat16"))
-    only = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else range(len(cases))
-    iters = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+    ap = argparse.ArgumentParser()
+    ap.add_argument("cases", nargs="?", default=None, help="comma-separated case indices (default: all)")
+    ap.add_argument("iters", nargs="?", type=int, default=200)
+    ap.add_argument("--tail", default="", help="comma-separated dense tail lengths, e.g. 0,128,1024,4096")
+    args = ap.parse_args()
+    only = [int(x) for x in args.cases.split(",")] if args.cases else range(len(cases))
+    tails = tuple(int(x) for x in args.tail.split(",")) if args.tail else ()
     for i in only:
-        run(*cases[i], iters=iters)
+        run(*cases[i], iters=args.iters, tails=tails)
