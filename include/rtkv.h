@@ -604,6 +604,40 @@ int rtkv_decode_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t
                                       const rtkv_dense_tail* tail, float* out_dev, void* workspace_dev,
                                       size_t workspace_bytes, void* stream);
 
+/* Multi-token step over one layer's PACKED KV followed by the dense tail: attention of T >= 1 new
+ * tokens per batch row, the multi-token form of rtkv_decode_attention_packed_tail.  NO WORKING
+ * REFERENCE COUNTERPART (modified_llama.py:83-102 concatenates and then compresses again with a
+ * non-square attention matrix); this is the plain causal attention a model computes over
+ * cat(cache, new tokens).  The tail already holds the T new tokens as its last T rows (append, then
+ * attend).  With r_b = min(rows[b], row_capacity) and n_b = clamp(tail->rows_dev[b], 0, tail->capacity),
+ * query t (0 <= t < T) of batch row b and query head h attends over
+ *   - every packed row j < r_b, K'/V' decoded from the codes exactly as rtkv_decode_attention_packed;
+ *   - the tail rows u < vis(b,t) = max(0, n_b - (T-1-t)), as stored:
+ * the new tokens are causal among themselves, everything older is fully visible, one softmax over
+ * the concatenation.  out[b,h,t,:] (fp32, [B, Hq, T, D] contiguous) is zeros where r_b + vis(b,t) == 0.
+ * Nothing at or past a count is read.  The packed-layer arguments are those of
+ * rtkv_decode_attention_packed_tail in the same order and with the same meaning, through bits[3];
+ * row_capacity == 0 (tail only; the packed pointers and bits may then be null) is allowed.  q is the
+ * model's post-RoPE [B, Hq, T, D] in the K/V dtype: element (b,h,t,d) at
+ * b*q_stride_b + h*q_stride_h + t*q_stride_t + d (strides in elements, rows 16-byte aligned).
+ * Arithmetic: dot products on the matrix core (v_mfma_f32_16x16x32) with fp32 accumulation; the
+ * softmax weights are rounded to the K/V dtype for the weights·V product, their sum stays fp32.
+ * Envelope: float16 and bfloat16, head_dim 128, F = Hkv*D a multiple of 512, Hq a multiple of Hkv,
+ * field widths 2/4/8/16, any B, 1 <= T with B*Hq*T < 2^29 — anything else RTKV_ERR_UNSUPPORTED.
+ * Workspace (16-byte aligned): rtkv_extend_workspace_size(B, Hq, Hkv, D, T, row_capacity,
+ * tail->capacity) bytes, non-decreasing in T and in both capacities.  RTKV_ERR_INVALID ("extend: ..."),
+ * checked on the host before any launch: a misaligned q, q stride, tail base or tail stride, a null
+ * rows_dev, a negative capacity, T < 1, a too-small workspace. */
+size_t rtkv_extend_workspace_size(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t T, int64_t row_capacity,
+                                  int64_t tail_capacity);
+int rtkv_extend_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t* packed_v_dev, int64_t packed_bytes,
+                                      const int64_t* row_offset_dev, const float* scale_zp_dev,
+                                      const int32_t* kept_index_dev, const uint8_t* labels_dev, int64_t B, int64_t S,
+                                      int64_t row_capacity, const int64_t* rows_dev, int64_t Hkv, int64_t D, int dtype,
+                                      const int32_t bits[3], const void* q_dev, int64_t q_stride_b, int64_t q_stride_h,
+                                      int64_t q_stride_t, int64_t Hq, int64_t T, float scale, const rtkv_dense_tail* tail,
+                                      float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Extension "rtkv-gq/1": per-channel outlier detection + per-head group-wise 2/4/8-bit pack.
  * NO REFERENCE COUNTERPART — the reference quantizes each token with one (scale, zero_point) over all H·D

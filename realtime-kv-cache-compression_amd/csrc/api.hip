@@ -699,6 +699,24 @@ int rtkv_decode_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t
                             workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
+size_t rtkv_extend_workspace_size(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t T, int64_t row_capacity,
+                                  int64_t tail_capacity) {
+  if (B < 1 || Hkv < 1 || Hq < Hkv || D < 1 || T < 1 || row_capacity < 0 || tail_capacity < 0) return 0;
+  return extend_workspace_bytes(B, Hq, Hkv, D, T, row_capacity, tail_capacity);
+}
+
+int rtkv_extend_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t* packed_v_dev, int64_t packed_bytes,
+                                      const int64_t* row_offset_dev, const float* scale_zp_dev,
+                                      const int32_t* kept_index_dev, const uint8_t* labels_dev, int64_t B, int64_t S,
+                                      int64_t row_capacity, const int64_t* rows_dev, int64_t Hkv, int64_t D, int dtype,
+                                      const int32_t bits[3], const void* q_dev, int64_t q_stride_b, int64_t q_stride_h,
+                                      int64_t q_stride_t, int64_t Hq, int64_t T, float scale, const rtkv_dense_tail* tail,
+                                      float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return launch_extend(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev, labels_dev,
+                       B, S, row_capacity, rows_dev, Hkv, D, dtype, bits, q_dev, q_stride_b, q_stride_h, q_stride_t, Hq, T,
+                       scale, tail, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+}
+
 int rtkv_gather_rows(const void* src_dev, int64_t B, int64_t S, int64_t row_bytes, const int32_t* kept_index_dev,
                      int64_t row_capacity, int64_t src_stride_b, void* dst_dev, int64_t dst_stride_b, int64_t src_stride_s,
                      const rtkv_layer_stats* stats_dev, void* stream) {

@@ -338,6 +338,13 @@ int launch_decode_tail(const uint8_t* codes_k, const uint8_t* codes_v, int64_t c
                        const void* q, int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out, void* ws,
                        size_t ws_bytes, hipStream_t st);
 
+size_t extend_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t T, int64_t cap, int64_t tail_cap);
+int launch_extend(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
+                  const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
+                  int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
+                  int64_t qsb, int64_t qsh, int64_t qst, int64_t Hq, int64_t T, float scale, const rtkv_dense_tail* tail,
+                  float* out, void* ws, size_t ws_bytes, hipStream_t st);
+
 int launch_tensor_params(const void* x, int dt, int64_t n_rows, int64_t row_len, const uint8_t* row_labels,
                          int label_value, int bits, float* scale_zp, void* ws, size_t ws_bytes, hipStream_t st);
 int launch_tensor_fake_quant(const void* x, int dt, int64_t n_rows, int64_t row_len, const uint8_t* row_labels,

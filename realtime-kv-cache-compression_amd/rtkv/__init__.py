@@ -6,13 +6,13 @@ class and method names.  All compute runs in librtkv.so (include/rtkv.h); there 
 """
 from . import _lib
 from .base_config import CompressionConfig
-from .compression_layers import (AdaptiveQuantization, CompressedKVCache, DecodeTail, decode_attention, load_packed,
+from .compression_layers import (AdaptiveQuantization, CompressedKVCache, DecodeTail, decode_attention, extend_attention, load_packed,
                                  save_packed, unpack_layer)
 from .dynamic_quantization import DynamicPrecisionQuantizer
 from .group_quant import GroupQuantConfig, GroupQuantKVCache, gq_compress
 from .engine import (LayerBuffers, LayerResult, Workspace, attention_lse, compress_layer, compress_layer_qk,
                      importance_qk_lse, params_from_config, prompt_length)
-from .model_side import CompressedDecodeAttention, CompressedPrefillAttention
+from .model_side import CompressedDecodeAttention, CompressedExtendAttention, CompressedPrefillAttention
 from .selective_propagation import SelectiveTokenPropagator
 from .token_importance import LayerWiseImportanceTracker, PromptGuidedImportanceScorer
 from .unified_compressor import CompressionHook, RealTimePrefillCompressor, UnifiedCompressor
@@ -21,7 +21,8 @@ __all__ = [
     "CompressionConfig", "RealTimePrefillCompressor", "UnifiedCompressor", "CompressionHook",
     "PromptGuidedImportanceScorer", "LayerWiseImportanceTracker", "DynamicPrecisionQuantizer",
     "SelectiveTokenPropagator", "CompressedKVCache", "AdaptiveQuantization", "unpack_layer", "decode_attention",
-    "save_packed", "load_packed", "CompressedPrefillAttention", "CompressedDecodeAttention", "DecodeTail",
+    "save_packed", "load_packed", "CompressedPrefillAttention", "CompressedDecodeAttention", "DecodeTail", "extend_attention",
+    "CompressedExtendAttention",
     "LayerBuffers", "LayerResult", "Workspace", "compress_layer", "compress_layer_qk", "importance_qk_lse", "attention_lse",
     "params_from_config", "prompt_length", "GroupQuantConfig", "GroupQuantKVCache", "gq_compress",
 ]

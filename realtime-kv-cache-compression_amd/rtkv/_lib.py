@@ -178,6 +178,10 @@ _SIGS = {
     "rtkv_decode_tail_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
     "rtkv_decode_attention_packed_tail": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64,
                                            c_i32, c_p, c_p, c_i64, ctypes.c_float, c_p, c_p, c_p, c_sz, c_p], c_i32),
+    "rtkv_extend_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
+    "rtkv_extend_attention_packed_tail": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64,
+                                           c_i32, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_float, c_p, c_p,
+                                           c_p, c_sz, c_p], c_i32),
 }
 EXPORTS = tuple(_SIGS)
 

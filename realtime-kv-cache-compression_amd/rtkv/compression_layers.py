@@ -76,6 +76,15 @@ class CompressedKVCache:
         return decode_attention(self.compression_info[layer_idx], q, num_kv_heads, scale,
                                 tail=self.tails.get(layer_idx))
 
+    def attend_chunk(self, layer_idx: int, q: torch.Tensor, num_kv_heads: int, scale: Optional[float] = None):
+        """Attention of the T newest tokens (q [B, Hq, T, D]; their K/V are already the last T rows of
+        the layer's tail) over the packed layer and the tail, causal among the new tokens: fp32
+        [B, Hq, T, D] (extend_attention)."""
+        t = self.tails.get(layer_idx)
+        if t is None:
+            raise ValueError(f"layer {layer_idx} has no appended tokens: append the chunk's K/V first")
+        return extend_attention(self.compression_info[layer_idx], q, num_kv_heads, t, scale)
+
     def append(self, layer_idx: int, k_new: torch.Tensor, v_new: torch.Tensor):
         """Append the dense K/V of newly generated tokens ([B, F] or [B, T, F], the layout
         compress_layer_kv_cache takes) behind the layer's packed rows (modified_llama.py:83-94: a
@@ -426,6 +435,88 @@ def _decode_attention_tail(p: dict, q: torch.Tensor, num_kv_heads: int, scale: O
                                                       qc.data_ptr(), Hq, sc, ctypes.byref(dt), out.data_ptr(),
                                                       ws.data_ptr(), ws.numel(), L.stream_ptr(dev)),
             "rtkv_decode_attention_packed_tail")
+    return out
+
+
+def extend_attention(p: dict, q: torch.Tensor, num_kv_heads: int, tail: DecodeTail,
+                     scale: Optional[float] = None) -> torch.Tensor:
+    """Attention of T new tokens per batch row over a packed layer followed by the dense tail
+    (rtkv_extend_attention_packed_tail).  q: [B, Hq, T, D] in the layer's dtype, post-RoPE; the tail
+    already holds the T new tokens as its last T rows (append, then attend).  Returns fp32
+    [B, Hq, T, D]: query t attends over every kept row and the tail rows u < max(0, n_b − (T−1−t)),
+    n_b the tail's count of batch row b — causal among the new tokens, everything older fully visible,
+    one softmax over the concatenation.  scale defaults to 1/sqrt(D).
+
+    The kernel takes float16 and bfloat16 with head_dim 128.  Anything else decode_attention takes
+    (float32 states, other head dims) is computed with no new kernel: T single-token steps of
+    decode_attention(..., tail=) over the same buffers with device-side counts n_b − (T−1−t) clamped
+    at 0 — the same result, at the cost of T decode steps."""
+    codes_k, codes_v = p["codes_k"], p["codes_v"]
+    L.require_device(codes_k, codes_v, q, tail.k, tail.v, tail.rows_dev)
+    dev = q.device
+    if q.dim() != 4:
+        raise ValueError(f"q must be [B, Hq, T, D], got {tuple(q.shape)}")
+    if q.dtype != p["dtype"]:
+        raise ValueError(f"q dtype {q.dtype} does not match the packed layer's {p['dtype']}")
+    B, Hq, T, D = q.shape
+    F = int(p["feature_dim"])
+    if T < 1:
+        raise ValueError("q holds no new token (T < 1)")
+    if num_kv_heads * D != F:
+        raise ValueError(f"num_kv_heads * head_dim = {num_kv_heads * D} != feature_dim {F}")
+    if num_kv_heads < 1 or Hq % num_kv_heads:
+        raise ValueError(f"{Hq} query heads are not a multiple of {num_kv_heads} kv heads")
+    if tail.k.dtype != q.dtype or tail.k.shape[0] != B or tail.k.shape[2] != F or tail.k.device != dev \
+            or tail.v.shape != tail.k.shape or tail.rows_dev.shape != (B,) or tail.rows_dev.dtype != torch.int64:
+        raise ValueError(f"tail [{tuple(tail.k.shape)} {tail.k.dtype}] does not match q's batch {B}, feature_dim {F}, "
+                         f"dtype {q.dtype}")
+    if q.dtype not in (torch.float16, torch.bfloat16) or D != 128:
+        # outside the kernel's envelope: T decode steps, step t seeing the tail up to its own token
+        out = torch.empty(B, Hq, T, D, dtype=torch.float32, device=dev)
+        n_b = tail.rows_dev.clamp(0, tail.capacity)
+        for t in range(T):
+            rows_t = (n_b - (T - 1 - t)).clamp_(min=0)
+            out[:, :, t] = _decode_attention_tail(p, q[:, :, t], num_kv_heads, scale,
+                                                  DecodeTail.from_tensors(tail.k, tail.v, rows_t))
+        return out
+    row_offset = p["row_offset"].contiguous()
+    scale_zp = p["scale_zp"].contiguous()
+    kept_index = p["kept_index"].contiguous()
+    labels = p["labels"].contiguous()
+    _check_dtypes("extend", p)
+    if kept_index.dim() != 2 or kept_index.shape[0] != B or len(p["rows"]) != B or labels.shape[0] != B \
+            or row_offset.shape[0] != B or scale_zp.shape[0] != B:
+        raise ValueError(f"q has {B} batch rows but the packed layer has {kept_index.shape[0]} "
+                         f"(rows {len(p['rows'])}, labels {labels.shape[0]})")
+    Sp = kept_index.shape[1]
+    if row_offset.shape != (B, Sp) or scale_zp.shape != (B, Sp, 4):
+        raise ValueError("packed layer: row_offset / scale_zp shapes disagree with kept_index")
+    if codes_k.numel() != codes_v.numel():
+        raise ValueError("codes_k and codes_v differ in size")
+    if any(int(r) < 0 or int(r) > Sp for r in p["rows"]):
+        raise ValueError(f"row counts {p['rows']} outside [0, {Sp}]")
+    S = labels.shape[1]
+    rows = p.get("_rows_dev")
+    if rows is None or rows.device != dev:
+        rows = p["_rows_dev"] = torch.tensor(p["rows"], dtype=torch.int64, device=dev)
+    if q.stride(3) != 1 or any(st % 8 for st in q.stride()[:3]) or q.data_ptr() % 16:
+        q = q.contiguous()
+    out = torch.empty(B, Hq, T, D, dtype=torch.float32, device=dev)
+    bits = (ctypes.c_int32 * 3)(*p["bits"])
+    cap = tail.capacity
+    dt = L.DenseTail(L.ptr(tail.k) if cap else 0, L.ptr(tail.v) if cap else 0, tail.rows_dev.data_ptr(), cap,
+                     tail.k.stride(0), tail.k.stride(1))
+    ws = torch.empty(L.lib().rtkv_extend_workspace_size(B, Hq, num_kv_heads, D, T, Sp, cap), dtype=torch.uint8,
+                     device=dev)
+    sc = float(scale) if scale is not None else 1.0 / float(D) ** 0.5
+    pk = (lambda t: t.data_ptr()) if Sp else (lambda t: 0)  # no packed row capacity: null packed pointers
+    L.check(L.lib().rtkv_extend_attention_packed_tail(pk(codes_k), pk(codes_v), codes_k.numel(), pk(row_offset),
+                                                      pk(scale_zp), pk(kept_index), pk(labels), B, S, Sp,
+                                                      pk(rows), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype], bits,
+                                                      q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), Hq, T, sc,
+                                                      ctypes.byref(dt), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      L.stream_ptr(dev)),
+            "rtkv_extend_attention_packed_tail")
     return out
 
 

@@ -173,6 +173,42 @@ class CompressedDecodeAttention:
         return out.to(query_states.dtype).reshape(B, 1, H * D)
 
 
+class CompressedExtendAttention:
+    """A multi-token step (q_len = T >= 1) over a CompressedKVCache whose layer holds the prefill's
+    packed rows: the next user turn of a chat, the verification of k draft tokens, a further chunk
+    of a prompt.  The reference has no working counterpart (modified_llama.py:83-102 concatenates
+    and then compresses again with a non-square attention matrix); this is the plain causal
+    attention over cat(cache, new tokens), the multi-token form of CompressedDecodeAttention:
+    the T tokens are appended to the layer's DecodeTail and each attends over the packed rows, the
+    older tail rows and the new tokens up to itself (rtkv_extend_attention_packed_tail)."""
+
+    def __init__(self, cache, num_heads: int, num_kv_heads: int, head_dim: int, layer_idx: int):
+        self.cache = cache
+        self.num_heads = num_heads
+        self.num_kv_heads = num_kv_heads
+        self.head_dim = head_dim
+        self.layer_idx = layer_idx
+
+    def __call__(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
+                 attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """query [B,Hq,T,D], key/value [B,Hkv,T,D] (post-RoPE) → attn_output [B, T, Hq·D] before
+        o_proj, in the query dtype.  Shapes are checked before anything is appended."""
+        if attention_mask is not None:
+            raise ValueError("CompressedExtendAttention takes no attention mask: the new tokens are causal "
+                             "among themselves and see everything older")
+        if query_states.dim() != 4 or key_states.dim() != 4:
+            raise ValueError("query_states [B,Hq,T,D] and key_states [B,Hkv,T,D] expected")
+        B, H, T, D = query_states.shape
+        Hkv = key_states.shape[1]
+        if H != self.num_heads or Hkv != self.num_kv_heads or D != self.head_dim or T < 1 \
+                or key_states.shape != (B, Hkv, T, D) or value_states.shape != key_states.shape:
+            raise ValueError("state shapes do not match the layer's head configuration and the query's q_len")
+        self.cache.append(self.layer_idx, key_states.transpose(1, 2).reshape(B, T, Hkv * D),
+                          value_states.transpose(1, 2).reshape(B, T, Hkv * D))
+        out = self.cache.attend_chunk(self.layer_idx, query_states, Hkv)
+        return out.to(query_states.dtype).transpose(1, 2).reshape(B, T, H * D)
+
+
 def split_attention_mask(attention_mask: torch.Tensor, B: int, S: int):
     """The model's additive mask [B or 1, 1, S, >=S] → (key_bias, valid_key): None, None for the plain
     causal mask; else the fp32 [B, S] key bias (0 real key, -inf padding key) and the bool [B, S]

@@ -8,7 +8,12 @@ HBM bytes / time (packed codes + per-row scale/zp + kept_index / row_offset + la
 generated tokens (rtkv_decode_attention_packed_tail) next to dense SDPA over cat(K', tail), with the
 rate of the added bytes 2·T·F·e / (t_T − t_0), t_0 the no-tail step.
 
-usage: decode_bench.py [cases e.g. 0,2] [iters] [--tail 0,128,1024,4096]"""
+--chunk T[,T...]: a multi-token step (rtkv_extend_attention_packed_tail) of T new tokens over the packed
+rows and a tail of `older` + T rows, next to the same work done as T single-token steps of
+rtkv_decode_attention_packed_tail (step t over the tail up to its own token), timed in the same run.
+`older` takes the values of --tail (default 0,1024).
+
+usage: decode_bench.py [cases e.g. 0,2] [iters] [--tail 0,128,1024,4096] [--chunk 1,4,16,64,256]"""
 import argparse
 import os
 import sys
@@ -65,7 +70,26 @@ def run_tails(pk, k2, v2, n, q, Hkv, Hq, D, us0, tails, iters):
               f"dense SDPA over cat(K', tail) {us_d:.1f} us", flush=True)
 
 
-def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200, tails=()):
+def run_chunks(pk, q1, Hkv, Hq, D, chunks, olders, iters):
+    """One call of T new tokens against T single-token steps over the same layer and tail."""
+    F = Hkv * D
+    for older in olders:
+        for T in chunks:
+            n = older + T
+            tk = torch.randn(1, n, F, device="cuda").to(q1.dtype)
+            tv = torch.randn(1, n, F, device="cuda").to(q1.dtype)
+            q = torch.randn(1, Hq, T, D, device="cuda").to(q1.dtype)
+            whole = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n], device="cuda"))
+            steps = [(q[:, :, t].contiguous(), rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n - (T - 1 - t)], device="cuda")))
+                     for t in range(T)]
+            it = max(10, iters // max(1, T // 8))
+            us = timed(lambda: rtkv.extend_attention(pk, q, Hkv, whole), iters)
+            us_1 = timed(lambda: [rtkv.decode_attention(pk, qt, Hkv, tail=tl) for qt, tl in steps], it)
+            print(f"    chunk T={T} older={older}: extend {us:.1f} us ({us / T:.1f} us/token) | {T} single steps {us_1:.1f} us "
+                  f"({us_1 / T:.1f} us/token) | ratio {us_1 / us:.2f}x", flush=True)
+
+
+def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200, tails=(), chunks=()):
     F = Hkv * D
     K, V = synth.kv(11, 1, S, F, dtype)
     W = synth.attention_slice(11, 1, 8, S, rtkv.prompt_length(S), dtype)
@@ -110,8 +134,10 @@ def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200, tails=()):
     print(f"S={S} Hkv={Hkv} Hq={Hq} {dtype}: kept {n}, packed {code_bytes/1e6:.2f} MB ({code_bytes*8/(2*n*F):.2f} bits/elem) "
           f"-> decode {us:.1f} us, {by/us/1e3:.0f} GB/s algorithmic | dense SDPA over K'/V' {us_d:.1f} us "
           f"({dense_by/1e6:.1f} MB, {dense_by/us_d/1e3:.0f} GB/s)", flush=True)
-    if tails:
+    if tails and not chunks:
         run_tails(pk, k2, v2, n, q, Hkv, Hq, D, us, tails, iters)
+    if chunks:
+        run_chunks(pk, q, Hkv, Hq, D, chunks, tails or (0, 1024), iters)
 
 
 if __name__ == "__main__":
@@ -122,8 +148,9 @@ if __name__ == "__main__":
     ap.add_argument("cases", nargs="?", default=None, help="comma-separated case indices (default: all)")
     ap.add_argument("iters", nargs="?", type=int, default=200)
     ap.add_argument("--tail", default="", help="comma-separated dense tail lengths, e.g. 0,128,1024,4096")
+    ap.add_argument("--chunk", default="", help="comma-separated numbers of new tokens per multi-token step, e.g. 1,4,16,64,256")
     args = ap.parse_args()
     only = [int(x) for x in args.cases.split(",")] if args.cases else range(len(cases))
     tails = tuple(int(x) for x in args.tail.split(",")) if args.tail else ()
     for i in only:
-        run(*cases[i], iters=args.iters, tails=tails)
+        run(*cases[i], iters=args.iters, tails=tails, chunks=tuple(int(x) for x in args.chunk.split(",")) if args.chunk else ())
