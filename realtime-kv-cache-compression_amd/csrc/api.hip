@@ -79,6 +79,79 @@ static FinalizeArgs finalize_args(const rtkv_layer_params* p, int64_t B, int64_t
   return a;
 }
 
+// ---- attention over the packed rows: one description of the layer, one set of host checks
+#define RTKV_ATTN_REQUIRE(cond, status, msg)                       \
+  do {                                                             \
+    if (!(cond)) {                                                 \
+      set_error(std::string("rtkv: ") + c.who + (msg));            \
+      return (status);                                             \
+    }                                                              \
+  } while (0)
+
+int check_attn_query(const AttnChecks& c, const PackedLayer& p, const void* q, int64_t Hq, const void* out) {
+  RTKV_ATTN_REQUIRE(q && out, RTKV_ERR_INVALID, "null pointer");
+  RTKV_ATTN_REQUIRE(p.B >= 1 && p.Hkv >= 1 && p.D >= 1 && Hq >= p.Hkv && Hq % p.Hkv == 0 && p.r.cap >= 0,
+                    RTKV_ERR_INVALID, "bad shape");
+  RTKV_ATTN_REQUIRE(p.B <= c.max_batch, RTKV_ERR_INVALID, "grid too large");
+  RTKV_ATTN_REQUIRE(((uintptr_t)q & 15) == 0, RTKV_ERR_INVALID, "q must be 16-byte aligned");
+  return RTKV_OK;
+}
+
+int check_attn_shape(const AttnChecks& c, const PackedLayer& p) {
+  if (c.dtypes) RTKV_ATTN_REQUIRE(p.dt >= 0 && p.dt < 32 && ((c.dtypes >> p.dt) & 1u), c.unsupported, "unsupported dtype");
+  if (c.head_dim) RTKV_ATTN_REQUIRE(p.D == c.head_dim, c.unsupported, "head_dim 128 only");
+  RTKV_ATTN_REQUIRE(p.D % 8 == 0 && 64 % (p.D / 8) == 0, c.unsupported, "head_dim must be 8·2^k with 8 <= head_dim <= 512");
+  RTKV_ATTN_REQUIRE((p.Hkv * p.D) % 512 == 0, c.unsupported, "Hkv*D must be a multiple of 512");
+  return RTKV_OK;
+}
+
+int check_dense_tail(const AttnChecks& c, const rtkv_dense_tail* tail, int64_t F, int64_t e) {
+  RTKV_ATTN_REQUIRE(tail != nullptr, RTKV_ERR_INVALID, "null pointer");
+  RTKV_ATTN_REQUIRE(tail->capacity >= 0, RTKV_ERR_INVALID, "negative tail capacity");
+  RTKV_ATTN_REQUIRE(tail->rows_dev != nullptr, RTKV_ERR_INVALID, "null tail rows_dev");
+  if (tail->capacity == 0) return RTKV_OK;
+  RTKV_ATTN_REQUIRE(tail->k_dev && tail->v_dev, RTKV_ERR_INVALID, "null tail pointer");
+  RTKV_ATTN_REQUIRE(((uintptr_t)tail->k_dev & 15) == 0 && ((uintptr_t)tail->v_dev & 15) == 0, RTKV_ERR_INVALID,
+                    "tail k_dev and v_dev must be 16-byte aligned");
+  RTKV_ATTN_REQUIRE(tail->stride_b >= 0 && tail->stride_s >= F, RTKV_ERR_INVALID,
+                    "tail stride_s below Hkv*D or negative stride_b");
+  RTKV_ATTN_REQUIRE((tail->stride_b * e) % 16 == 0 && (tail->stride_s * e) % 16 == 0, RTKV_ERR_INVALID,
+                    "tail strides must keep rows 16-byte aligned");
+  return RTKV_OK;
+}
+
+int check_workspace(const AttnChecks& c, const void* ws, size_t ws_bytes, size_t need) {
+  RTKV_ATTN_REQUIRE(ws && ((uintptr_t)ws & (c.ws_align - 1)) == 0 && ws_bytes >= need, RTKV_ERR_INVALID,
+                    "workspace too small");
+  return RTKV_OK;
+}
+
+int check_packed_layer(const AttnChecks& c, PackedLayer& p) {
+  PackedRows& r = p.r;
+  r.w[0] = r.w[1] = r.w[2] = 0;
+  if (r.cap == 0 && !c.packed_required) return RTKV_OK;  // no packed rows: nothing of the layer is read
+  RTKV_ATTN_REQUIRE(r.codes_k && r.codes_v && r.row_offset && r.scale_zp && r.kept_index && r.labels && r.rows && p.bits,
+                    RTKV_ERR_INVALID, "null pointer");
+  RTKV_ATTN_REQUIRE(r.S >= 1 && r.cap >= 1 && r.codes_bytes >= 0, RTKV_ERR_INVALID, "bad shape");
+  RTKV_ATTN_REQUIRE(((uintptr_t)r.scale_zp & 15) == 0, RTKV_ERR_INVALID, "scale_zp must be 16-byte aligned");
+  for (int k = 0; k < 3; ++k) {
+    r.w[k] = field_width(p.dt, p.bits[k]);
+    RTKV_ATTN_REQUIRE(r.w[k] == 2 || r.w[k] == 4 || r.w[k] == 8 || r.w[k] == 16, c.unsupported,
+                      "packed field widths 2/4/8/16 only");
+  }
+  return RTKV_OK;
+}
+#undef RTKV_ATTN_REQUIRE
+
+// the packed layer of an attention entry point, from its ABI arguments (check_packed_layer fills r.w)
+static PackedLayer packed_layer(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes,
+                                const int64_t* row_offset, const float* scale_zp, const int32_t* kept_index,
+                                const uint8_t* labels, int64_t B, int64_t S, int64_t cap, const int64_t* rows,
+                                int64_t Hkv, int64_t D, int dt, const int32_t* bits) {
+  return PackedLayer{{codes_k, codes_v, codes_bytes, row_offset, scale_zp, kept_index, labels, rows, S, cap, {0, 0, 0}},
+                     B, Hkv, D, dt, bits};
+}
+
 }  // namespace rtkv
 
 using namespace rtkv;
@@ -674,10 +747,9 @@ int rtkv_decode_attention_packed(const uint8_t* packed_k_dev, const uint8_t* pac
                                  int64_t D, int dtype, const int32_t bits[3], const void* q_dev, int64_t Hq,
                                  float scale, float* out_dev, void* workspace_dev, size_t workspace_bytes,
                                  void* stream) {
-  RTKV_REQUIRE(bits != nullptr, "null bits");
-  return launch_decode(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev, labels_dev, B, S,
-                       row_capacity, rows_dev, Hkv, D, dtype, bits, q_dev, Hq, scale, out_dev, workspace_dev,
-                       workspace_bytes, (hipStream_t)stream);
+  PackedLayer p = packed_layer(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev,
+                               labels_dev, B, S, row_capacity, rows_dev, Hkv, D, dtype, bits);
+  return launch_decode(p, q_dev, Hq, scale, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t rtkv_decode_tail_workspace_size(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t row_capacity,
@@ -693,10 +765,9 @@ int rtkv_decode_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t
                                       const int32_t bits[3], const void* q_dev, int64_t Hq, float scale,
                                       const rtkv_dense_tail* tail, float* out_dev, void* workspace_dev,
                                       size_t workspace_bytes, void* stream) {
-  RTKV_REQUIRE(bits != nullptr || row_capacity == 0, "null bits");
-  return launch_decode_tail(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev,
-                            labels_dev, B, S, row_capacity, rows_dev, Hkv, D, dtype, bits, q_dev, Hq, scale, tail, out_dev,
-                            workspace_dev, workspace_bytes, (hipStream_t)stream);
+  PackedLayer p = packed_layer(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev,
+                               labels_dev, B, S, row_capacity, rows_dev, Hkv, D, dtype, bits);
+  return launch_decode_tail(p, q_dev, Hq, scale, tail, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t rtkv_extend_workspace_size(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t T, int64_t row_capacity,
@@ -712,9 +783,10 @@ int rtkv_extend_attention_packed_tail(const uint8_t* packed_k_dev, const uint8_t
                                       const int32_t bits[3], const void* q_dev, int64_t q_stride_b, int64_t q_stride_h,
                                       int64_t q_stride_t, int64_t Hq, int64_t T, float scale, const rtkv_dense_tail* tail,
                                       float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  return launch_extend(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev, labels_dev,
-                       B, S, row_capacity, rows_dev, Hkv, D, dtype, bits, q_dev, q_stride_b, q_stride_h, q_stride_t, Hq, T,
-                       scale, tail, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream);
+  PackedLayer p = packed_layer(packed_k_dev, packed_v_dev, packed_bytes, row_offset_dev, scale_zp_dev, kept_index_dev,
+                               labels_dev, B, S, row_capacity, rows_dev, Hkv, D, dtype, bits);
+  return launch_extend(p, q_dev, q_stride_b, q_stride_h, q_stride_t, Hq, T, scale, tail, out_dev, workspace_dev,
+                       workspace_bytes, (hipStream_t)stream);
 }
 
 int rtkv_gather_rows(const void* src_dev, int64_t B, int64_t S, int64_t row_bytes, const int32_t* kept_index_dev,

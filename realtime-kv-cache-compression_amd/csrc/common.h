@@ -325,25 +325,56 @@ int launch_unpack(const uint8_t* packed, const int64_t* row_offset, const float*
                   const int64_t* rows, int64_t H, int64_t D, int dt, const int32_t bits[3], void* out,
                   int64_t ob, int64_t os, int64_t oh, hipStream_t st);
 
+// ---- attention over a layer's packed rows (decode.hip, decode_tail.hip, extend.hip)
+// What the attention kernels read of a packed layer; embedded in their argument structs.
+struct PackedRows {
+  const uint8_t* codes_k;
+  const uint8_t* codes_v;
+  int64_t codes_bytes;        // size of each code buffer
+  const int64_t* row_offset;  // [B, cap]
+  const float* scale_zp;      // [B, cap, 4]
+  const int32_t* kept_index;  // [B, cap]
+  const uint8_t* labels;      // [B, S]
+  const int64_t* rows;        // [B]
+  int64_t S, cap;
+  int w[3];                   // field width of each class (check_packed_layer)
+};
+// A packed layer as the C ABI passes it (api.hip builds it once); check_packed_layer fills r.w.
+struct PackedLayer {
+  PackedRows r;
+  int64_t B, Hkv, D;
+  int dt;
+  const int32_t* bits;        // [3], may be null when r.cap == 0
+};
+// What differs between the entry points' argument checks.
+struct AttnChecks {
+  const char* who;        // message prefix: "decode: " or "extend: "
+  int unsupported;        // status of a dtype / head_dim / Hkv*D / field-width refusal
+  unsigned dtypes;        // bit dt set: the dtype is taken; 0: not checked (any other value is read as float32)
+  int64_t head_dim;       // the one head_dim taken, or 0: any 8·2^k up to 512
+  int64_t max_batch;
+  bool packed_required;   // cap >= 1 and non-null packed pointers (false: cap == 0 with null pointers is fine)
+  size_t ws_align;        // required alignment of the workspace, bytes
+};
+// Each sets the error message and returns a status other than RTKV_OK on the first failed check; none
+// touches the device.  check_attn_query: q, out, the head counts and the batch; check_attn_shape: the
+// shapes the kernels take (dtype, Hkv*D, head_dim); check_workspace: `need` bytes at c.ws_align.
+int check_attn_query(const AttnChecks& c, const PackedLayer& p, const void* q, int64_t Hq, const void* out);
+int check_attn_shape(const AttnChecks& c, const PackedLayer& p);
+int check_dense_tail(const AttnChecks& c, const rtkv_dense_tail* tail, int64_t F, int64_t elem_bytes);
+int check_workspace(const AttnChecks& c, const void* ws, size_t ws_bytes, size_t need);
+int check_packed_layer(const AttnChecks& c, PackedLayer& p);
+
 size_t decode_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t cap);
-int launch_decode(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                  const float* scale_zp,
-                  const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S, int64_t cap,
-                  const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
-                  int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_decode(PackedLayer& p, const void* q, int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes,
+                  hipStream_t st);
 size_t decode_tail_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t cap, int64_t tail_cap);
-int launch_decode_tail(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                       const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
-                       int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3],
-                       const void* q, int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out, void* ws,
-                       size_t ws_bytes, hipStream_t st);
+int launch_decode_tail(PackedLayer& p, const void* q, int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out,
+                       void* ws, size_t ws_bytes, hipStream_t st);
 
 size_t extend_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t T, int64_t cap, int64_t tail_cap);
-int launch_extend(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                  const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
-                  int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
-                  int64_t qsb, int64_t qsh, int64_t qst, int64_t Hq, int64_t T, float scale, const rtkv_dense_tail* tail,
-                  float* out, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_extend(PackedLayer& p, const void* q, int64_t qsb, int64_t qsh, int64_t qst, int64_t Hq, int64_t T,
+                  float scale, const rtkv_dense_tail* tail, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 
 int launch_tensor_params(const void* x, int dt, int64_t n_rows, int64_t row_len, const uint8_t* row_labels,
                          int label_value, int bits, float* scale_zp, void* ws, size_t ws_bytes, hipStream_t st);

@@ -1,16 +1,28 @@
-// decode.hip — decode attention over packed KV: the split merge, the launch
-// geometry and the C-ABI side; the split kernel and its design notes are in decode_kernel.h (fp16
-// instantiations: decode_f16.hip).
+// decode.hip — decode attention over packed KV: the launch geometry of the split
+// kernels, the merge of a decode step's splits (the packed rows' and, for decode_tail.hip, the dense
+// tail's behind them) and rtkv_decode_attention_packed; the split kernel and its design notes are
+// in decode_kernel.h (fp16 instantiations: decode_f16.hip).
 #include "decode_kernel.h"
 
 namespace rtkv {
 
 namespace {
 
-// out[b, hq, d] = Σ_s e^{m_s - m*} acc_s / Σ_s e^{m_s - m*} l_s over the splits.  Workgroup of
-// 16 features × 64 split phases (phase p takes splits ≡ p mod 64), combined through LDS.
+struct MergeArgs {
+  const float* part_m;  // [B][G][n][Hkv]
+  const float* part_l;
+  const float* part_acc;  // [B][G][n][F]
+  int n;
+  int Hkv, D, G;
+  float* out;           // [B, Hq, D] fp32
+};
+
+// out[b, hq, d] = Σ_s e^{m_s - m*} acc_s / Σ_s e^{m_s - m*} l_s over the n splits of the list.
+// Workgroup of 16 features × 64 split phases (phase p takes splits ≡ p mod 64, in order), combined
+// through LDS.  A split without rows (m = -inf, l = acc = 0) adds exact zeros, so a step with an
+// empty tail has the bits of the step without one.
 constexpr int kMF = 16, kMP = 64;
-__global__ __launch_bounds__(kMF * kMP) void decode_merge_kernel(DecodeArgs a) {
+__global__ __launch_bounds__(kMF * kMP) void decode_merge_kernel(MergeArgs a) {
   __shared__ float red[3][kMP][kMF];
   const int F = a.Hkv * a.D;
   const int fl = threadIdx.x % kMF, ph = threadIdx.x / kMF;
@@ -18,9 +30,9 @@ __global__ __launch_bounds__(kMF * kMP) void decode_merge_kernel(DecodeArgs a) {
   const int g = blockIdx.y, b = blockIdx.z;
   const bool ok = f < F;
   const int hk = ok ? f / a.D : 0, d = f - hk * a.D;
-  const int64_t base = ((int64_t)b * a.G + g) * a.splits;
+  const int64_t base = ((int64_t)b * a.G + g) * a.n;
   float mm = -INFINITY;
-  for (int s = ph; s < a.splits; s += kMP) mm = fmaxf(mm, a.part_m[(base + s) * a.Hkv + hk]);
+  for (int s = ph; s < a.n; s += kMP) mm = fmaxf(mm, a.part_m[(base + s) * a.Hkv + hk]);
   red[0][ph][fl] = mm;
   __syncthreads();
   mm = red[0][0][fl];
@@ -29,7 +41,7 @@ __global__ __launch_bounds__(kMF * kMP) void decode_merge_kernel(DecodeArgs a) {
   float num = 0.f, den = 0.f;
   if (mm != -INFINITY && ok) {
 #pragma unroll 4
-    for (int s = ph; s < a.splits; s += kMP) {
+    for (int s = ph; s < a.n; s += kMP) {
       const float ms = a.part_m[(base + s) * a.Hkv + hk];
       const float fct = ms == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(ms - mm);
       num += fct * a.part_acc[(base + s) * F + f];
@@ -57,70 +69,54 @@ size_t decode_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int
   return (size_t)(B * G * s) * (size_t)(2 * Hkv + Hkv * D) * sizeof(float) + 256;
 }
 
-int launch_decode_splits(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                         const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
-                         int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3],
-                         const void* q, int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st,
-                         DecodeArgs& a) {
-  RTKV_REQUIRE(codes_k && codes_v && row_offset && scale_zp && kept_index && labels && rows && q && out,
-               "decode: null pointer");
-  RTKV_REQUIRE(B >= 1 && S >= 1 && cap >= 1 && Hkv >= 1 && D >= 1 && Hq >= Hkv && Hq % Hkv == 0,
-               "decode: bad shape");
-  RTKV_REQUIRE(B <= 65535, "decode: grid too large");
-  const int64_t F = Hkv * D;
-  const int64_t G = Hq / Hkv;
-  RTKV_REQUIRE(F % 512 == 0, "decode: Hkv*D must be a multiple of 512");
-  RTKV_REQUIRE(D % 8 == 0 && 64 % (D / 8) == 0, "decode: head_dim must be 8·2^k with 8 <= head_dim <= 512");
-  std::memset(&a, 0, sizeof(a));
-  for (int k = 0; k < 3; ++k) {
-    a.w[k] = field_width(dt, bits[k]);
-    RTKV_REQUIRE(a.w[k] == 2 || a.w[k] == 4 || a.w[k] == 8 || a.w[k] == 16,
-                 "decode: packed field widths 2/4/8/16 only");
-  }
-  RTKV_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)scale_zp & 15) == 0, "decode: q and scale_zp must be 16-byte aligned");
-  const int splits = decode_splits(B, G, F, cap);
-  RTKV_REQUIRE(ws && ws_bytes >= decode_workspace_bytes(B, Hq, Hkv, D, cap), "decode: workspace too small");
-  RTKV_REQUIRE(codes_bytes >= 0, "decode: negative code buffer size");
-  a.codes_k = codes_k; a.codes_v = codes_v; a.codes_bytes = codes_bytes; a.row_offset = row_offset; a.scale_zp = scale_zp;
-  a.kept_index = kept_index; a.labels = labels; a.rows = rows;
-  a.S = S; a.cap = cap; a.Hkv = (int)Hkv; a.D = (int)D; a.G = (int)G;
-  a.q = q; a.scale = scale * 1.4426950408889634f; a.splits = splits;
-  float* p = static_cast<float*>(ws);
-  a.part_m = p;
-  p += B * G * splits * Hkv;
-  a.part_l = p;
-  p += B * G * splits * Hkv;
-  a.part_acc = p;
-  a.out = out;
+int launch_decode_splits(const PackedLayer& p, const void* q, int64_t Hq, float scale, const DecodeParts& parts,
+                         hipStream_t st) {
+  const int64_t B = p.B, F = p.Hkv * p.D, G = Hq / p.Hkv;
   const DecodeShape sh = decode_shape(F, G);
+  DecodeArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.pk = p.r;
+  a.Hkv = (int)p.Hkv; a.D = (int)p.D; a.G = (int)G;
   a.HG = sh.hg;
   a.GS = sh.gs;
-  a.nrest = (int)((int64_t)splits * a.HG * B);
+  a.q = q; a.scale = scale * 1.4426950408889634f;
+  a.splits = decode_splits(B, G, F, p.r.cap);
+  a.n = parts.n;
+  a.part_m = parts.m; a.part_l = parts.l; a.part_acc = parts.acc;
+  a.nrest = (int)((int64_t)a.splits * a.HG * B);
   const int64_t nblk = ((int64_t)a.nrest + 7) / 8 * 8 * a.GS;
   RTKV_REQUIRE(nblk < (1ll << 31), "decode: grid too large");
   const dim3 grid((unsigned)nblk);
   const size_t lds = (size_t)kDW * 64 * sh.nch * sh.gq * 10 * sizeof(float);
-  int rc;
-  if (dt == RTKV_F16) rc = launch_decode_split_f16(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  else if (dt == RTKV_BF16) rc = launch_decode_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  else rc = launch_decode_split<RTKV_F32>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  return rc;
+  if (p.dt == RTKV_F16) return launch_decode_split_f16(a, sh.nch, sh.gq, (int)p.D, grid, lds, st);
+  if (p.dt == RTKV_BF16) return launch_decode_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)p.D, grid, lds, st);
+  return launch_decode_split<RTKV_F32>(a, sh.nch, sh.gq, (int)p.D, grid, lds, st);
 }
 
-int launch_decode(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                  const float* scale_zp,
-                  const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S, int64_t cap,
-                  const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
-                  int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
-  DecodeArgs a;
-  const int rc = launch_decode_splits(codes_k, codes_v, codes_bytes, row_offset, scale_zp, kept_index, labels, B, S, cap,
-                                      rows, Hkv, D, dt, bits, q, Hq, scale, out, ws, ws_bytes, st, a);
-  if (rc != RTKV_OK) return rc;
+int launch_decode_merge(const DecodeParts& parts, int64_t B, int64_t Hq, int64_t Hkv, int64_t D, float* out,
+                        hipStream_t st) {
   const int64_t F = Hkv * D, G = Hq / Hkv;
+  const MergeArgs a = {parts.m, parts.l, parts.acc, parts.n, (int)Hkv, (int)D, (int)G, out};
   hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)((F + kMF - 1) / kMF), (unsigned)G, (unsigned)B),
                      dim3(kMF * kMP), 0, st, a);
   RTKV_HIP_CHECK(hipGetLastError());
   return RTKV_OK;
+}
+
+int launch_decode(PackedLayer& p, const void* q, int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes,
+                  hipStream_t st) {
+  // this entry point checks neither the dtype value (anything but fp16 / bf16 is read as fp32) nor the
+  // workspace's alignment
+  const AttnChecks c = {"decode: ", RTKV_ERR_INVALID, 0u, 0, 65535, true, 1};
+  int rc;
+  if ((rc = check_attn_query(c, p, q, Hq, out)) != RTKV_OK) return rc;
+  if ((rc = check_attn_shape(c, p)) != RTKV_OK) return rc;
+  if ((rc = check_packed_layer(c, p)) != RTKV_OK) return rc;
+  if ((rc = check_workspace(c, ws, ws_bytes, decode_workspace_bytes(p.B, Hq, p.Hkv, p.D, p.r.cap))) != RTKV_OK) return rc;
+  const int64_t G = Hq / p.Hkv;
+  const DecodeParts parts = decode_parts(ws, p.B, G, p.Hkv, decode_splits(p.B, G, p.Hkv * p.D, p.r.cap));
+  if ((rc = launch_decode_splits(p, q, Hq, scale, parts, st)) != RTKV_OK) return rc;
+  return launch_decode_merge(parts, p.B, Hq, p.Hkv, p.D, out, st);
 }
 
 }  // namespace rtkv

@@ -19,8 +19,9 @@
 // lanes of one head reduce q·k with DPP adds; every lane keeps the online-softmax state (m, l) and
 // 8 value accumulators per (query head, chunk).  fp16 rows are dequantized with packed half2
 // arithmetic (bit-identical: each op of dequant<F16> is one rounded fp16 op), bf16 rows with
-// v_cvt_pk_bf16_f32 roundings and v_dot2_f32_bf16.  The 4 waves merge in LDS; a second kernel
-// merges the splits.
+// v_cvt_pk_bf16_f32 roundings and v_dot2_f32_bf16.  The 4 waves merge in LDS
+// (merge_waves_write_partial, shared with the dense tail's split kernel of decode_tail.hip) and write
+// one entry of the step's list of partials; a second kernel (decode.hip) merges the list.
 #pragma once
 
 #include "common.h"
@@ -32,40 +33,42 @@
 namespace rtkv {
 
 struct DecodeArgs {
-  const uint8_t* codes_k;
-  const uint8_t* codes_v;
-  int64_t codes_bytes;        // size of each code buffer
-  const int64_t* row_offset;  // [B, cap]
-  const float* scale_zp;      // [B, cap, 4]
-  const int32_t* kept_index;  // [B, cap]
-  const uint8_t* labels;      // [B, S]
-  const int64_t* rows;        // [B]
-  int64_t S, cap;
+  PackedRows pk;
   int Hkv, D, G;              // G = Hq / Hkv
   int HG;                     // head groups: F / (512·NCH)
   int GS;                     // query-head groups: G / GQ
   int nrest;                  // splits · HG · B
-  int w[3];                   // field width of each class
   const void* q;              // [B, Hq, D] (dtype)
   float scale;
-  int splits;
-  float* part_m;              // [B][G][splits][Hkv]
+  int splits;                 // splits of the packed rows
+  int n;                      // splits in the step's list of partials (the packed splits, then the tail's)
+  float* part_m;              // [B][G][n][Hkv]
   float* part_l;
-  float* part_acc;            // [B][G][splits][F]
-  float* out;                 // [B, Hq, D] fp32
+  float* part_acc;            // [B][G][n][F]
 };
 
 // launches decode_split_kernel<RTKV_F16, …> (decode_f16.hip, its own flags)
 int launch_decode_split_f16(const DecodeArgs& a, int nch, int gq, int D, dim3 grid, size_t lds, hipStream_t st);
 
-// The packed half of a decode step without the merge (decode.hip): checks the arguments, fills `a`
-// with the partials laid out at the start of ws and launches the split kernels.  launch_decode
-// merges them; the dense-tail entry point (decode_tail.hip) merges them with the tail's partials.
-int launch_decode_splits(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                         const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
-                         int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3],
-                         const void* q, int64_t Hq, float scale, float* out, void* ws, size_t ws_bytes, hipStream_t st,
-                         DecodeArgs& a);
+// The partials of one decode step: per (b, g) one list of n splits, the packed rows' first and the
+// dense tail's behind them.
+struct DecodeParts {
+  float* m;                   // [B][G][n][Hkv]
+  float* l;
+  float* acc;                 // [B][G][n][F]
+  int n;
+};
+inline DecodeParts decode_parts(void* ws, int64_t B, int64_t G, int64_t Hkv, int n) {
+  float* p = static_cast<float*>(ws);
+  return DecodeParts{p, p + B * G * n * Hkv, p + 2 * B * G * n * Hkv, n};
+}
+// The packed half of a decode step (decode.hip): the split kernels over the (checked) layer's rows
+// write splits 0 .. decode_splits(cap) − 1 of `parts`.
+int launch_decode_splits(const PackedLayer& p, const void* q, int64_t Hq, float scale, const DecodeParts& parts,
+                         hipStream_t st);
+// out[b, hq, d] from the n splits of `parts` (decode.hip)
+int launch_decode_merge(const DecodeParts& parts, int64_t B, int64_t Hq, int64_t Hkv, int64_t D, float* out,
+                        hipStream_t st);
 
 namespace {
 
@@ -222,6 +225,46 @@ __device__ __forceinline__ float lane_f(float v, int t) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), t));
 }
 
+// The end of a split kernel (the packed rows' or the dense tail's), after every wave has stored
+// (m, l, acc) of its units to LDS ([kDW][64][GQ·NCH][10] floats) and the workgroup has met at a
+// barrier: wave 0 merges the kDW waves and writes split s of the list of a.n partials of (b, g).
+// The accumulators are in the slot order of dtype SLOT (slot_elem); A is the kernel's argument
+// struct (G, Hkv, n, part_m, part_l, part_acc).  The store to LDS, the barrier and the other waves'
+// return stay in the kernels, and D and lph come from them: with either inside this function
+// register counts of decode_split_kernel moved (profiles/attn_refactor_resources.txt).
+template <int SLOT, int NCH, int GQ, typename A>
+__device__ __forceinline__ void merge_waves_write_partial(const A& a, const float* lds, int lane, int gs, int b, int s,
+                                                          int c0, int F, int D, int lph) {
+  constexpr int kU = GQ * NCH;
+#pragma unroll
+  for (int j = 0; j < GQ; ++j) {
+    const int g = gs * GQ + j;
+    const int64_t pbase = ((int64_t)b * a.G + g) * a.n + s;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int un = j * NCH + k;
+      float mm = -INFINITY;
+      for (int v = 0; v < kDW; ++v) mm = fmaxf(mm, lds[(((size_t)v * 64 + lane) * kU + un) * 10]);
+      float ll = 0.f, aa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int v = 0; v < kDW; ++v) {
+        const float* src = lds + (((size_t)v * 64 + lane) * kU + un) * 10;
+        const float f = src[0] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(src[0] - mm);
+        ll += f * src[1];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) aa[e] += f * src[2 + e];
+      }
+      const int f0 = (c0 + k * 64 + lane) * 8, hk = f0 / D;
+      if ((lane % lph) == 0) {
+        a.part_m[pbase * a.Hkv + hk] = mm;
+        a.part_l[pbase * a.Hkv + hk] = ll;
+      }
+      float* pa = a.part_acc + pbase * F + f0;
+#pragma unroll
+      for (int sl = 0; sl < 8; ++sl) pa[slot_elem<SLOT>(sl)] = aa[sl];
+    }
+  }
+}
+
 // One workgroup per (split s, head group hg, batch row b) × query-head group gs (GQ query heads of
 // each kv head), ids arranged so the GS workgroups that read the same rows share id mod 8, i.e.
 // one XCD and its L2.
@@ -230,8 +273,7 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
   using S_ = typename Dt<DT>::S;
   constexpr bool kH = DT == RTKV_F16;
   constexpr bool kB = DT == RTKV_BF16;
-  constexpr int kU = GQ * NCH;    // (query head, chunk) units per lane
-  extern __shared__ float lds[];  // [kDW][64][kU][10]: m, l, acc[8] per unit
+  extern __shared__ float lds[];  // [kDW][64][GQ·NCH][10]: m, l, acc[8] per (query head, chunk) unit
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int id = blockIdx.x, hi = id >> 3;
   const int gs = hi % a.GS;
@@ -240,7 +282,7 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
   const int s = rest % a.splits, t1 = rest / a.splits, hg = t1 % a.HG, b = t1 / a.HG;
   const int F = a.HG * NCH * 512, D = a.D, lph = D / 8;  // lanes per head within one chunk column
   const int c0 = hg * NCH * 64;                            // first chunk of this head group
-  const int64_t nrows = a.rows[b] < a.cap ? (a.rows[b] > 0 ? a.rows[b] : 0) : a.cap;
+  const int64_t nrows = a.pk.rows[b] < a.pk.cap ? (a.pk.rows[b] > 0 ? a.pk.rows[b] : 0) : a.pk.cap;
   const int64_t per = (nrows + a.splits - 1) / a.splits;
   const int64_t r0 = (int64_t)s * per, r1 = r0 + per < nrows ? r0 + per : nrows;
   const int Hq = a.Hkv * a.G;
@@ -407,14 +449,14 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
   // the row list's last row (no successor) takes its class.  A span that matches no width (corrupt
   // metadata) leaves the row out.  The next 64 rows' metadata is in flight while this batch's rows are
   // processed.
-  const int64_t bcap = (int64_t)b * a.cap;
+  const int64_t bcap = (int64_t)b * a.pk.cap;
   auto meta = [&](int64_t jb, int64_t& off, int64_t& offn, float4& sz) {
     const int64_t jr = jb + (int64_t)kDW * lane;
     const bool ok = jr < r1, nx = jr + 1 < nrows;
     const int64_t rj = bcap + (ok ? jr : jb);
-    off = a.row_offset[rj];
-    offn = (ok && nx) ? a.row_offset[rj + 1] : -1;
-    sz = *reinterpret_cast<const float4*>(a.scale_zp + rj * 4);
+    off = a.pk.row_offset[rj];
+    offn = (ok && nx) ? a.pk.row_offset[rj + 1] : -1;
+    sz = *reinterpret_cast<const float4*>(a.pk.scale_zp + rj * 4);
   };
   int64_t m_off = 0, m_offn = -1;
   float4 m_sz = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -430,13 +472,13 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
       const int fb8 = F / 8;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
-        if (span == (int64_t)fb8 * a.w[c]) wl = a.w[c];
+        if (span == (int64_t)fb8 * a.pk.w[c]) wl = a.pk.w[c];
       const bool lastrow = ok && jr + 1 == nrows;
       if (__ballot(lastrow)) {  // the list's last row: its class (kept index → label)
-        const int ki0 = a.kept_index[bcap + (lastrow ? jr : jb)];
-        const int ki = ki0 < 0 ? 0 : (ki0 >= a.S ? (int)a.S - 1 : ki0);
-        const int lab = a.labels[(int64_t)b * a.S + ki];
-        if (lastrow) wl = lab == 2 ? a.w[2] : (lab == 1 ? a.w[1] : a.w[0]);
+        const int ki0 = a.pk.kept_index[bcap + (lastrow ? jr : jb)];
+        const int ki = ki0 < 0 ? 0 : (ki0 >= a.pk.S ? (int)a.pk.S - 1 : ki0);
+        const int lab = a.pk.labels[(int64_t)b * a.pk.S + ki];
+        if (lastrow) wl = lab == 2 ? a.pk.w[2] : (lab == 1 ? a.pk.w[1] : a.pk.w[0]);
       }
     }
     if (jb + 64 * kDW < r1) meta(jb + 64 * kDW, m_off, m_offn, m_sz);  // the next batch, in flight meanwhile
@@ -463,9 +505,9 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
         const int64_t o = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)off_hi, t) << 32) |
                                     (uint32_t)__builtin_amdgcn_readlane((int)off_lo, t));
         const int64_t nbr = (int64_t)(F / 8) * W;
-        const int nb = (o >= 0 && o + nbr <= a.codes_bytes) ? (int)nbr : 0;  // out of range: zero codes
-        const auto sk = __builtin_amdgcn_make_buffer_rsrc((void*)(a.codes_k + o), (short)0, nb, 0x00020000);
-        const auto sv = __builtin_amdgcn_make_buffer_rsrc((void*)(a.codes_v + o), (short)0, nb, 0x00020000);
+        const int nb = (o >= 0 && o + nbr <= a.pk.codes_bytes) ? (int)nbr : 0;  // out of range: zero codes
+        const auto sk = __builtin_amdgcn_make_buffer_rsrc((void*)(a.pk.codes_k + o), (short)0, nb, 0x00020000);
+        const auto sv = __builtin_amdgcn_make_buffer_rsrc((void*)(a.pk.codes_v + o), (short)0, nb, 0x00020000);
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
           const int vo = (c0 + k * 64 + lane) * W;
@@ -511,8 +553,8 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
     by_width(std::integral_constant<int, 8>{});
     by_width(std::integral_constant<int, 16>{});
   }
-  // ---- merge the kDW waves in LDS, then write this split's partial
-  float* mine = lds + ((size_t)wave * 64 + lane) * kU * 10;
+  // ---- the kDW waves meet in LDS; wave 0 merges them and writes this split's partial
+  float* mine = lds + ((size_t)wave * 64 + lane) * (GQ * NCH) * 10;
 #pragma unroll
   for (int j = 0; j < GQ; ++j) {
 #pragma unroll
@@ -526,33 +568,7 @@ __global__ __launch_bounds__(64 * kDW) void decode_split_kernel(DecodeArgs a) {
   }
   __syncthreads();
   if (wave != 0) return;
-#pragma unroll
-  for (int j = 0; j < GQ; ++j) {
-    const int g = gs * GQ + j;
-    const int64_t pbase = ((int64_t)b * a.G + g) * a.splits + s;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-      const int un = j * NCH + k;
-      float mm = -INFINITY;
-      for (int v = 0; v < kDW; ++v) mm = fmaxf(mm, lds[(((size_t)v * 64 + lane) * kU + un) * 10]);
-      float ll = 0.f, aa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int v = 0; v < kDW; ++v) {
-        const float* src = lds + (((size_t)v * 64 + lane) * kU + un) * 10;
-        const float f = src[0] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(src[0] - mm);
-        ll += f * src[1];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) aa[e] += f * src[2 + e];
-      }
-      const int f0 = (c0 + k * 64 + lane) * 8, hk = f0 / D;
-      if ((lane % lph) == 0) {
-        a.part_m[pbase * a.Hkv + hk] = mm;
-        a.part_l[pbase * a.Hkv + hk] = ll;
-      }
-      float* pa = a.part_acc + pbase * F + f0;
-#pragma unroll
-      for (int sl = 0; sl < 8; ++sl) pa[slot_elem<DT>(sl)] = aa[sl];
-    }
-  }
+  merge_waves_write_partial<DT, NCH, GQ>(a, lds, lane, gs, b, s, c0, F, D, lph);
 }
 
 // the split kernel of one dtype for the lane shape (NCH chunks, GQ query heads) and head_dim

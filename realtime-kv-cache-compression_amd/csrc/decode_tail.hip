@@ -5,8 +5,8 @@
 // the cache and attends over all of it (modified_llama.py:83-94, 152): at step t the keys are the
 // kept, dequantized prefill rows followed by the t dense rows generated so far.  Here the packed
 // rows go through the split kernel of decode_kernel.h unchanged, the tail rows through
-// decode_tail_kernel below as further splits, and one merge pass takes both sets of (m, l, acc)
-// partials: one softmax over the concatenation.
+// decode_tail_kernel below as further splits of the same list of (m, l, acc) partials, and the merge
+// of decode.hip takes the whole list: one softmax over the concatenation.
 //
 // Tail kernel: the decomposition of the packed kernel without the decoding.  One workgroup of 4
 // waves per (tail split s, head group hg, batch row b, query-head group gs); wave v takes tail rows
@@ -33,9 +33,10 @@ struct TailArgs {
   const void* q;              // [B, Hq, D] (dtype)
   float scale;                // · log2(e)
   int splits;                 // tail splits
-  float* part_m;              // [B][G][splits][Hkv]
+  int n;                      // splits in the step's list of partials
+  float* part_m;              // [B][G][n][Hkv], from the first tail split on
   float* part_l;
-  float* part_acc;            // [B][G][splits][F]
+  float* part_acc;            // [B][G][n][F], likewise
 };
 
 template <int DT, int NCH, int GQ, int LPH>
@@ -43,9 +44,8 @@ __global__ __launch_bounds__(64 * kDW) void decode_tail_kernel(TailArgs a) {
   using S_ = typename Dt<DT>::S;
   constexpr bool kH = DT == RTKV_F16;
   constexpr bool kB = DT == RTKV_BF16;
-  constexpr int kU = GQ * NCH;    // (query head, chunk) units per lane
   constexpr int PD = DT == RTKV_F32 ? 2 : 4;  // rows in flight (≤ 32 VGPRs of K and V at NCH 2)
-  extern __shared__ float lds[];  // [kDW][64][kU][10]: m, l, acc[8] per unit
+  extern __shared__ float lds[];  // [kDW][64][GQ·NCH][10]: m, l, acc[8] per (query head, chunk) unit
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int id = blockIdx.x, hi = id >> 3;
   const int gs = hi % a.GS;
@@ -194,8 +194,8 @@ __global__ __launch_bounds__(64 * kDW) void decode_tail_kernel(TailArgs a) {
       }
     }
   }
-  // ---- merge the kDW waves in LDS, then write this split's partial (decode_kernel.h's layout)
-  float* mine = lds + ((size_t)wave * 64 + lane) * kU * 10;
+  // ---- the kDW waves meet in LDS; wave 0 merges them and writes this split's partial
+  float* mine = lds + ((size_t)wave * 64 + lane) * (GQ * NCH) * 10;
 #pragma unroll
   for (int j = 0; j < GQ; ++j) {
 #pragma unroll
@@ -209,33 +209,7 @@ __global__ __launch_bounds__(64 * kDW) void decode_tail_kernel(TailArgs a) {
   }
   __syncthreads();
   if (wave != 0) return;
-#pragma unroll
-  for (int j = 0; j < GQ; ++j) {
-    const int g = gs * GQ + j;
-    const int64_t pbase = ((int64_t)b * a.G + g) * a.splits + s;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-      const int un = j * NCH + k;
-      float mm = -INFINITY;
-      for (int v = 0; v < kDW; ++v) mm = fmaxf(mm, lds[(((size_t)v * 64 + lane) * kU + un) * 10]);
-      float ll = 0.f, aa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int v = 0; v < kDW; ++v) {
-        const float* src = lds + (((size_t)v * 64 + lane) * kU + un) * 10;
-        const float f = src[0] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(src[0] - mm);
-        ll += f * src[1];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) aa[e] += f * src[2 + e];
-      }
-      const int f0 = (c0 + k * 64 + lane) * 8, hk = f0 / D;
-      if ((lane % lph) == 0) {
-        a.part_m[pbase * a.Hkv + hk] = mm;
-        a.part_l[pbase * a.Hkv + hk] = ll;
-      }
-      float* pa = a.part_acc + pbase * F + f0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pa[e] = aa[e];
-    }
-  }
+  merge_waves_write_partial<RTKV_F32, NCH, GQ>(a, lds, lane, gs, b, s, c0, F, D, lph);  // acc in element order
 }
 
 template <int DT>
@@ -254,117 +228,31 @@ int launch_tail_split(const TailArgs& a, int nch, int gq, int D, dim3 grid, size
   RTKV_REQUIRE(false, "decode: unsupported lane shape");
 }
 
-// decode_merge_kernel (decode.hip) over two sets of partials: the sp packed splits, then the st
-// tail splits, as one list of sp + st splits.  Same geometry and the same arithmetic per split, so
-// with an empty tail (every tail partial m = -inf, l = acc = 0) the result has the bits of the
-// packed-only merge.
-struct TailMergeArgs {
-  const float* pm;  // packed partials [B][G][sp][Hkv], [B][G][sp][F]
-  const float* pl;
-  const float* pa;
-  const float* tm;  // tail partials [B][G][st][Hkv], [B][G][st][F]
-  const float* tl;
-  const float* ta;
-  int sp, st;
-  int Hkv, D, G;
-  float* out;       // [B, Hq, D] fp32
-};
-constexpr int kMF = 16, kMP = 64;
-__global__ __launch_bounds__(kMF * kMP) void decode_tail_merge_kernel(TailMergeArgs a) {
-  __shared__ float red[3][kMP][kMF];
-  const int F = a.Hkv * a.D;
-  const int fl = threadIdx.x % kMF, ph = threadIdx.x / kMF;
-  const int f = blockIdx.x * kMF + fl;
-  const int g = blockIdx.y, b = blockIdx.z;
-  const bool ok = f < F;
-  const int hk = ok ? f / a.D : 0, d = f - hk * a.D;
-  const int64_t bg = (int64_t)b * a.G + g;
-  const int n = a.sp + a.st;
-  // split s of the list: its m and l entry, and its acc entry
-  auto ml = [&](int s) { return s < a.sp ? (bg * a.sp + s) * a.Hkv + hk : (bg * a.st + (s - a.sp)) * a.Hkv + hk; };
-  auto ac = [&](int s) { return s < a.sp ? (bg * a.sp + s) * F + f : (bg * a.st + (s - a.sp)) * F + f; };
-  float mm = -INFINITY;
-  for (int s = ph; s < n; s += kMP) mm = fmaxf(mm, (s < a.sp ? a.pm : a.tm)[ml(s)]);
-  red[0][ph][fl] = mm;
-  __syncthreads();
-  mm = red[0][0][fl];
-#pragma unroll
-  for (int p = 1; p < kMP; ++p) mm = fmaxf(mm, red[0][p][fl]);
-  float num = 0.f, den = 0.f;
-  if (mm != -INFINITY && ok) {
-    for (int s = ph; s < n; s += kMP) {
-      const bool pk = s < a.sp;
-      const float ms = (pk ? a.pm : a.tm)[ml(s)];
-      const float fct = ms == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(ms - mm);
-      num += fct * (pk ? a.pa : a.ta)[ac(s)];
-      den += fct * (pk ? a.pl : a.tl)[ml(s)];
-    }
-  }
-  red[1][ph][fl] = num;
-  red[2][ph][fl] = den;
-  __syncthreads();
-  if (ph != 0 || !ok) return;
-#pragma unroll
-  for (int p = 1; p < kMP; ++p) {
-    num += red[1][p][fl];
-    den += red[2][p][fl];
-  }
-  const int Hq = a.Hkv * a.G;
-  a.out[((int64_t)b * Hq + (int64_t)hk * a.G + g) * a.D + d] = den > 0.f ? num / den : 0.f;
-}
-
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
-// bytes of the tail partials: B·G·splits·(2·Hkv + F) floats
-size_t tail_part_bytes(int64_t B, int64_t G, int64_t Hkv, int64_t D, int splits) {
-  return (size_t)(B * G * splits) * (size_t)(2 * Hkv + Hkv * D) * sizeof(float);
-}
-
 }  // namespace
 
+// The partials are one list of n = sp + st splits per (b, g): B·G·(sp + st)·(2·Hkv + F) floats.  The size
+// below is that of two separate lists, the packed one rounded up to 256 bytes, and so never smaller:
+//   align256(4·B·G·sp·(2·Hkv + F) + 256) + 4·B·G·st·(2·Hkv + F) + 256 >= 4·B·G·(sp + st)·(2·Hkv + F).
 size_t decode_tail_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int64_t cap, int64_t tail_cap) {
   const int64_t G = Hkv > 0 ? Hq / Hkv : 1;
-  const size_t packed = cap >= 1 ? align256(decode_workspace_bytes(B, Hq, Hkv, D, cap)) : 0;
-  return packed + tail_part_bytes(B, G, Hkv, D, decode_splits(B, G, Hkv * D, tail_cap)) + 256;
+  const size_t packed = cap >= 1 ? (decode_workspace_bytes(B, Hq, Hkv, D, cap) + 255) / 256 * 256 : 0;
+  const size_t st = decode_splits(B, G, Hkv * D, tail_cap);
+  return packed + (size_t)(B * G) * st * (size_t)(2 * Hkv + Hkv * D) * sizeof(float) + 256;
 }
 
-int launch_decode_tail(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                       const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
-                       int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3],
-                       const void* q, int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out, void* ws,
-                       size_t ws_bytes, hipStream_t st) {
-  RTKV_REQUIRE(tail && q && out, "decode: null pointer");
-  RTKV_REQUIRE(B >= 1 && Hkv >= 1 && D >= 1 && Hq >= Hkv && Hq % Hkv == 0 && cap >= 0, "decode: bad shape");
-  RTKV_REQUIRE(B <= 65535, "decode: grid too large");
-  RTKV_REQUIRE(dt == RTKV_F32 || dt == RTKV_F16 || dt == RTKV_BF16, "decode: unsupported dtype");
-  const int64_t F = Hkv * D, G = Hq / Hkv;
-  RTKV_REQUIRE(F % 512 == 0, "decode: Hkv*D must be a multiple of 512");
-  RTKV_REQUIRE(D % 8 == 0 && 64 % (D / 8) == 0, "decode: head_dim must be 8·2^k with 8 <= head_dim <= 512");
-  RTKV_REQUIRE(((uintptr_t)q & 15) == 0, "decode: q must be 16-byte aligned");
-  RTKV_REQUIRE(tail->capacity >= 0, "decode: negative tail capacity");
-  RTKV_REQUIRE(tail->rows_dev != nullptr, "decode: null tail rows_dev");
-  const int64_t e = dtype_bytes(dt);
-  if (tail->capacity > 0) {
-    RTKV_REQUIRE(tail->k_dev && tail->v_dev, "decode: null tail pointer");
-    RTKV_REQUIRE(((uintptr_t)tail->k_dev & 15) == 0 && ((uintptr_t)tail->v_dev & 15) == 0,
-                 "decode: tail k_dev and v_dev must be 16-byte aligned");
-    RTKV_REQUIRE(tail->stride_b >= 0 && tail->stride_s >= F, "decode: tail stride_s below Hkv*D or negative stride_b");
-    RTKV_REQUIRE((tail->stride_b * e) % 16 == 0 && (tail->stride_s * e) % 16 == 0,
-                 "decode: tail strides must keep rows 16-byte aligned");
-  }
-  RTKV_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= decode_tail_workspace_bytes(B, Hq, Hkv, D, cap, tail->capacity),
-               "decode: workspace too small");
-  TailMergeArgs mg;
-  std::memset(&mg, 0, sizeof(mg));
-  size_t used = 0;
-  if (cap >= 1) {  // the packed rows: the split kernels of rtkv_decode_attention_packed, same arguments
-    DecodeArgs pa;
-    used = align256(decode_workspace_bytes(B, Hq, Hkv, D, cap));
-    const int rc = launch_decode_splits(codes_k, codes_v, codes_bytes, row_offset, scale_zp, kept_index, labels, B, S, cap,
-                                        rows, Hkv, D, dt, bits, q, Hq, scale, out, ws, used, st, pa);
-    if (rc != RTKV_OK) return rc;
-    mg.pm = pa.part_m; mg.pl = pa.part_l; mg.pa = pa.part_acc; mg.sp = pa.splits;
-  }
+int launch_decode_tail(PackedLayer& p, const void* q, int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out,
+                       void* ws, size_t ws_bytes, hipStream_t st) {
+  const AttnChecks c = {"decode: ", RTKV_ERR_INVALID, 1u << RTKV_F32 | 1u << RTKV_F16 | 1u << RTKV_BF16, 0, 65535,
+                        false, 4};
+  int rc;
+  if ((rc = check_attn_query(c, p, q, Hq, out)) != RTKV_OK) return rc;
+  if ((rc = check_attn_shape(c, p)) != RTKV_OK) return rc;
+  const int64_t B = p.B, Hkv = p.Hkv, D = p.D, F = Hkv * D, G = Hq / Hkv;
+  if ((rc = check_dense_tail(c, tail, F, dtype_bytes(p.dt))) != RTKV_OK) return rc;
+  if ((rc = check_workspace(c, ws, ws_bytes, decode_tail_workspace_bytes(B, Hq, Hkv, D, p.r.cap, tail->capacity))) != RTKV_OK)
+    return rc;
+  if ((rc = check_packed_layer(c, p)) != RTKV_OK) return rc;
+  const int sp = p.r.cap >= 1 ? decode_splits(B, G, F, p.r.cap) : 0;
   const DecodeShape sh = decode_shape(F, G);
   TailArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -375,27 +263,21 @@ int launch_decode_tail(const uint8_t* codes_k, const uint8_t* codes_v, int64_t c
   a.q = q; a.scale = scale * 1.4426950408889634f;
   a.splits = decode_splits(B, G, F, tail->capacity);
   a.nrest = (int)((int64_t)a.splits * a.HG * B);
-  float* p = reinterpret_cast<float*>(static_cast<char*>(ws) + used);
-  a.part_m = p;
-  p += B * G * a.splits * Hkv;
-  a.part_l = p;
-  p += B * G * a.splits * Hkv;
-  a.part_acc = p;
+  const DecodeParts parts = decode_parts(ws, B, G, Hkv, sp + a.splits);
+  if (sp > 0 && (rc = launch_decode_splits(p, q, Hq, scale, parts, st)) != RTKV_OK) return rc;
+  a.n = parts.n;  // the tail's splits follow the sp packed ones
+  a.part_m = parts.m + (int64_t)sp * Hkv;
+  a.part_l = parts.l + (int64_t)sp * Hkv;
+  a.part_acc = parts.acc + (int64_t)sp * F;
   const int64_t nblk = ((int64_t)a.nrest + 7) / 8 * 8 * a.GS;
   RTKV_REQUIRE(nblk < (1ll << 31), "decode: grid too large");
   const dim3 grid((unsigned)nblk);
   const size_t lds = (size_t)kDW * 64 * sh.nch * sh.gq * 10 * sizeof(float);
-  int rc;
-  if (dt == RTKV_F16) rc = launch_tail_split<RTKV_F16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  else if (dt == RTKV_BF16) rc = launch_tail_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
+  if (p.dt == RTKV_F16) rc = launch_tail_split<RTKV_F16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
+  else if (p.dt == RTKV_BF16) rc = launch_tail_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
   else rc = launch_tail_split<RTKV_F32>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
   if (rc != RTKV_OK) return rc;
-  mg.tm = a.part_m; mg.tl = a.part_l; mg.ta = a.part_acc; mg.st = a.splits;
-  mg.Hkv = (int)Hkv; mg.D = (int)D; mg.G = (int)G; mg.out = out;
-  hipLaunchKernelGGL(decode_tail_merge_kernel, dim3((unsigned)((F + kMF - 1) / kMF), (unsigned)G, (unsigned)B),
-                     dim3(kMF * kMP), 0, st, mg);
-  RTKV_HIP_CHECK(hipGetLastError());
-  return RTKV_OK;
+  return launch_decode_merge(parts, B, Hq, Hkv, D, out, st);
 }
 
 }  // namespace rtkv

@@ -26,7 +26,7 @@
 // compare on the slot index.  The row sum l stays fp32 from the unrounded exponentials; the running
 // max is raised lazily (slack 8).  The 4 waves merge through LDS at the end, one query tile at a
 // time, and write (m, l, acc[D]) per (b, query head, t, split); extend_merge_kernel combines the
-// splits with the arithmetic of decode_tail_merge_kernel.
+// splits with the arithmetic of decode_merge_kernel (decode.hip).
 //
 // Bounds: B·Hkv·passes·splits < 2^31 workgroups and B·Hq·T < 2^29 query rows.
 #include "decode_kernel.h"
@@ -79,22 +79,13 @@ constexpr int kXMinRows = 128;     // rows per split at least: one 32-key tile p
 constexpr int kXPassMax = 32;      // query rows per pass at most (NQT = 2: 252 VGPRs; NQT = 4 spills)
 
 struct ExtendArgs {
-  const uint8_t* codes_k;
-  const uint8_t* codes_v;
-  int64_t codes_bytes;
-  const int64_t* row_offset;  // [B, cap]
-  const float* scale_zp;      // [B, cap, 4]
-  const int32_t* kept_index;  // [B, cap]
-  const uint8_t* labels;      // [B, S]
-  const int64_t* rows;        // [B]
-  int64_t S, cap;
+  PackedRows pk;
   const void* tk;             // tail: element (b, u, h, d) at b·tsb + u·tss + h·D + d
   const void* tv;
   const int64_t* trows;       // [B]
   int64_t tcap, tsb, tss;
   int Hkv, G, T;
   int npass, sp, st;          // passes of 16·NQT query rows; packed splits, then tail splits
-  int w[3];
   const void* q;              // element (b, h, t, d) at b·qsb + h·qsh + t·qst + d
   int64_t qsb, qsh, qst;
   float scale;                // · log2(e)
@@ -294,33 +285,33 @@ __global__ __launch_bounds__(64 * kDW, 2) void extend_split_kernel(ExtendArgs a)
 
   if (s < a.sp) {
     // ---------------------------------------------------------------- packed rows of split s
-    const int64_t nrows = a.rows[b] < a.cap ? (a.rows[b] > 0 ? a.rows[b] : 0) : a.cap;
+    const int64_t nrows = a.pk.rows[b] < a.pk.cap ? (a.pk.rows[b] > 0 ? a.pk.rows[b] : 0) : a.pk.cap;
     const int64_t per = (nrows + a.sp - 1) / a.sp;
     const int64_t r0 = (int64_t)s * per, r1 = r0 + per < nrows ? r0 + per : nrows;
     const int64_t pw = r1 > r0 ? (r1 - r0 + kDW - 1) / kDW : 0;
     const int64_t w0 = r0 + wave * pw, w1 = w0 + pw < r1 ? w0 + pw : r1;
-    const int64_t bcap = (int64_t)b * a.cap;
+    const int64_t bcap = (int64_t)b * a.pk.cap;
     const int F = a.Hkv * kXD;
     int fill = 0;  // key slots of the image in use (wave-uniform)
     for (int64_t jb = w0; jb < w1; jb += 64) {
       const int64_t jr = jb + lane;
       const bool ok = jr < w1;
       const int64_t rj = bcap + (ok ? jr : jb);
-      const int64_t off = a.row_offset[rj];
-      const int64_t offn = (ok && jr + 1 < nrows) ? a.row_offset[rj + 1] : -1;
-      const float4 sz = *reinterpret_cast<const float4*>(a.scale_zp + rj * 4);
+      const int64_t off = a.pk.row_offset[rj];
+      const int64_t offn = (ok && jr + 1 < nrows) ? a.pk.row_offset[rj + 1] : -1;
+      const float4 sz = *reinterpret_cast<const float4*>(a.pk.scale_zp + rj * 4);
       // a row's width from its byte span (rows are back to back); the list's last row from its class
       int wl = 0;
       {
         const int64_t span = offn - off;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-          if (span == (int64_t)(F / 8) * a.w[c]) wl = a.w[c];
+          if (span == (int64_t)(F / 8) * a.pk.w[c]) wl = a.pk.w[c];
         if (ok && jr + 1 == nrows) {
-          const int ki0 = a.kept_index[rj];
-          const int ki = ki0 < 0 ? 0 : (ki0 >= a.S ? (int)a.S - 1 : ki0);
-          const int lab = a.labels[(int64_t)b * a.S + ki];
-          wl = lab == 2 ? a.w[2] : (lab == 1 ? a.w[1] : a.w[0]);
+          const int ki0 = a.pk.kept_index[rj];
+          const int ki = ki0 < 0 ? 0 : (ki0 >= a.pk.S ? (int)a.pk.S - 1 : ki0);
+          const int lab = a.pk.labels[(int64_t)b * a.pk.S + ki];
+          wl = lab == 2 ? a.pk.w[2] : (lab == 1 ? a.pk.w[1] : a.pk.w[0]);
         }
       }
       const uint32_t off_lo = (uint32_t)off, off_hi = (uint32_t)(off >> 32);
@@ -358,13 +349,13 @@ __global__ __launch_bounds__(64 * kDW, 2) void extend_split_kernel(ExtendArgs a)
             vzp[i] = __shfl(sz.w, src, kWave);
             const int64_t o = (int64_t)(((uint64_t)hi << 32) | lo);
             const int64_t nbr = (int64_t)(F / 8) * W;
-            const bool inb = mine[i] && o >= 0 && o + nbr <= a.codes_bytes;  // out of range: zero codes
+            const bool inb = mine[i] && o >= 0 && o + nbr <= a.pk.codes_bytes;  // out of range: zero codes
             xk[i] = ChunkCodes<W>{};
             xv[i] = ChunkCodes<W>{};
             if (inb) {
               const int64_t bo = o + (int64_t)(hk * 16 + c16) * W;
-              xk[i] = load_codes_global<W>(a.codes_k + bo);
-              xv[i] = load_codes_global<W>(a.codes_v + bo);
+              xk[i] = load_codes_global<W>(a.pk.codes_k + bo);
+              xv[i] = load_codes_global<W>(a.pk.codes_v + bo);
             }
           }
 #pragma unroll
@@ -482,7 +473,7 @@ __global__ __launch_bounds__(64 * kDW, 2) void extend_split_kernel(ExtendArgs a)
 }
 
 // One workgroup of D threads per (b, query head, t): the splits' (m, l, acc) into out, with the
-// arithmetic of decode_tail_merge_kernel (max, exp2 factors, num / den, zeros for no key).  The
+// arithmetic of decode_merge_kernel (max, exp2 factors, num / den, zeros for no key).  The
 // factors are computed once, a split per thread, and kept in LDS; thread d then sums its column.
 __global__ __launch_bounds__(kXD) void extend_merge_kernel(ExtendArgs a) {
   __shared__ float w[kXTargetWgs + 1];
@@ -571,71 +562,45 @@ size_t extend_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D, int
   return (size_t)parts * (size_t)(2 + D) * sizeof(float) + 256;
 }
 
-int launch_extend(const uint8_t* codes_k, const uint8_t* codes_v, int64_t codes_bytes, const int64_t* row_offset,
-                  const float* scale_zp, const int32_t* kept_index, const uint8_t* labels, int64_t B, int64_t S,
-                  int64_t cap, const int64_t* rows, int64_t Hkv, int64_t D, int dt, const int32_t bits[3], const void* q,
-                  int64_t qsb, int64_t qsh, int64_t qst, int64_t Hq, int64_t T, float scale, const rtkv_dense_tail* tail,
-                  float* out, void* ws, size_t ws_bytes, hipStream_t st) {
-  RTKV_REQUIRE(tail && q && out, "extend: null pointer");
+int launch_extend(PackedLayer& p, const void* q, int64_t qsb, int64_t qsh, int64_t qst, int64_t Hq, int64_t T,
+                  float scale, const rtkv_dense_tail* tail, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  // refusals of the kernel's envelope are RTKV_ERR_UNSUPPORTED, and come after every RTKV_ERR_INVALID
+  // check of the query, the tail and the workspace
+  const AttnChecks c = {"extend: ", RTKV_ERR_UNSUPPORTED, 1u << RTKV_F16 | 1u << RTKV_BF16, kXD, INT64_MAX, false, 16};
+  int rc;
+  if ((rc = check_attn_query(c, p, q, Hq, out)) != RTKV_OK) return rc;
   RTKV_REQUIRE(T >= 1, "extend: T must be at least 1");
-  RTKV_REQUIRE(B >= 1 && Hkv >= 1 && D >= 1 && Hq >= Hkv && Hq % Hkv == 0 && cap >= 0, "extend: bad shape");
-  RTKV_REQUIRE(tail->capacity >= 0, "extend: negative tail capacity");
-  RTKV_REQUIRE(tail->rows_dev != nullptr, "extend: null tail rows_dev");
-  RTKV_REQUIRE(((uintptr_t)q & 15) == 0 && qsb % 8 == 0 && qsh % 8 == 0 && qst % 8 == 0 && qsb >= 0 && qsh >= 0 && qst >= 0,
+  RTKV_REQUIRE(qsb % 8 == 0 && qsh % 8 == 0 && qst % 8 == 0 && qsb >= 0 && qsh >= 0 && qst >= 0,
                "extend: q and its strides must keep rows 16-byte aligned");
-  const int64_t F = Hkv * D, G = Hq / Hkv;
-  if (tail->capacity > 0) {
-    RTKV_REQUIRE(tail->k_dev && tail->v_dev, "extend: null tail pointer");
-    RTKV_REQUIRE(((uintptr_t)tail->k_dev & 15) == 0 && ((uintptr_t)tail->v_dev & 15) == 0,
-                 "extend: tail k_dev and v_dev must be 16-byte aligned");
-    RTKV_REQUIRE(tail->stride_b >= 0 && tail->stride_s >= F, "extend: tail stride_s below Hkv*D or negative stride_b");
-    RTKV_REQUIRE(tail->stride_b % 8 == 0 && tail->stride_s % 8 == 0, "extend: tail strides must keep rows 16-byte aligned");
-  }
+  const int64_t B = p.B, Hkv = p.Hkv, D = p.D, G = Hq / Hkv;
+  if ((rc = check_dense_tail(c, tail, Hkv * D, 2)) != RTKV_OK) return rc;
   RTKV_REQUIRE(B * Hq * T < (1ll << 31) / 4, "extend: too many query rows");
-  RTKV_REQUIRE(ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= extend_workspace_bytes(B, Hq, Hkv, D, T, cap, tail->capacity),
-               "extend: workspace too small");
-  auto unsupported = [](const char* msg) {
-    set_error(std::string("rtkv: ") + msg);
-    return RTKV_ERR_UNSUPPORTED;
-  };
-  if (dt != RTKV_F16 && dt != RTKV_BF16) return unsupported("extend: float16 and bfloat16 only");
-  if (D != kXD) return unsupported("extend: head_dim 128 only");
-  if (F % 512 != 0) return unsupported("extend: Hkv*D must be a multiple of 512");
+  if ((rc = check_workspace(c, ws, ws_bytes, extend_workspace_bytes(B, Hq, Hkv, D, T, p.r.cap, tail->capacity))) != RTKV_OK)
+    return rc;
+  if ((rc = check_attn_shape(c, p)) != RTKV_OK) return rc;
+  if ((rc = check_packed_layer(c, p)) != RTKV_OK) return rc;
+  const ExtendPlan pl = extend_plan(B, Hkv, G, T, p.r.cap, tail->capacity);
+  const int64_t nq = B * Hq * T;
   ExtendArgs a;
   std::memset(&a, 0, sizeof(a));
-  if (cap >= 1) {
-    RTKV_REQUIRE(codes_k && codes_v && row_offset && scale_zp && kept_index && labels && rows && bits,
-                 "extend: null pointer");
-    RTKV_REQUIRE(S >= 1 && codes_bytes >= 0, "extend: bad shape");
-    RTKV_REQUIRE(((uintptr_t)scale_zp & 15) == 0, "extend: scale_zp must be 16-byte aligned");
-    for (int k = 0; k < 3; ++k) {
-      a.w[k] = field_width(dt, bits[k]);
-      if (!(a.w[k] == 2 || a.w[k] == 4 || a.w[k] == 8 || a.w[k] == 16))
-        return unsupported("extend: packed field widths 2/4/8/16 only");
-    }
-  }
-  const ExtendPlan p = extend_plan(B, Hkv, G, T, cap, tail->capacity);
-  const int64_t nq = B * Hq * T;
-  a.codes_k = codes_k; a.codes_v = codes_v; a.codes_bytes = codes_bytes; a.row_offset = row_offset; a.scale_zp = scale_zp;
-  a.kept_index = kept_index; a.labels = labels; a.rows = rows; a.S = S; a.cap = cap;
+  a.pk = p.r;
   a.tk = tail->k_dev; a.tv = tail->v_dev; a.trows = tail->rows_dev;
   a.tcap = tail->capacity; a.tsb = tail->stride_b; a.tss = tail->stride_s;
   a.Hkv = (int)Hkv; a.G = (int)G; a.T = (int)T;
-  a.npass = p.npass; a.sp = p.sp; a.st = p.st;
+  a.npass = pl.npass; a.sp = pl.sp; a.st = pl.st;
   a.q = q; a.qsb = qsb; a.qsh = qsh; a.qst = qst;
   a.scale = scale * 1.4426950408889634f;
   a.part_ml = static_cast<float*>(ws);
-  a.part_acc = a.part_ml + (nq * (p.sp + p.st) * 2 + 3) / 4 * 4;
+  a.part_acc = a.part_ml + (nq * (pl.sp + pl.st) * 2 + 3) / 4 * 4;
   a.out = out;
-  const int nsplit = p.sp + p.st;
+  const int nsplit = pl.sp + pl.st;
   RTKV_REQUIRE(nsplit <= kXTargetWgs, "extend: too many splits");
   if (nsplit > 0) {
-    const int64_t nblk = B * Hkv * p.npass * nsplit;
+    const int64_t nblk = B * Hkv * pl.npass * nsplit;
     RTKV_REQUIRE(nblk < (1ll << 31), "extend: grid too large");
     const dim3 grid((unsigned)nblk);
-    int rc = RTKV_OK;
-    if (dt == RTKV_F16) rc = p.nqt == 1 ? launch_extend_split<RTKV_F16, 1>(a, grid, st) : launch_extend_split<RTKV_F16, 2>(a, grid, st);
-    else rc = p.nqt == 1 ? launch_extend_split<RTKV_BF16, 1>(a, grid, st) : launch_extend_split<RTKV_BF16, 2>(a, grid, st);
+    if (p.dt == RTKV_F16) rc = pl.nqt == 1 ? launch_extend_split<RTKV_F16, 1>(a, grid, st) : launch_extend_split<RTKV_F16, 2>(a, grid, st);
+    else rc = pl.nqt == 1 ? launch_extend_split<RTKV_BF16, 1>(a, grid, st) : launch_extend_split<RTKV_BF16, 2>(a, grid, st);
     if (rc != RTKV_OK) return rc;
   }
   hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)nq), dim3(kXD), 0, st, a);

@@ -111,6 +111,10 @@ def stats_bytes(B: int) -> int:
     return ctypes.sizeof(LayerStatsHeader) + B * ctypes.sizeof(BatchStats) + TIMES_BYTES
 
 
+# The packed layer as the attention entry points take it: codes_k, codes_v, codes bytes, row_offset, scale_zp,
+# kept_index, labels, B, S, row capacity, rows, Hkv, D, dtype, bits
+_PACKED = [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i32, c_p]
+
 _SIGS = {
     "rtkv_version": ([], ctypes.c_char_p),
     "rtkv_last_error": ([], ctypes.c_char_p),
@@ -173,15 +177,13 @@ _SIGS = {
     "rtkv_allgather_packed": ([c_p, c_p, c_i64, c_i64, c_p, c_p], c_i32),
     "rtkv_gather_rows": ([c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p], c_i32),
     "rtkv_decode_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
-    "rtkv_decode_attention_packed": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i32, c_p,
-                                      c_p, c_i64, ctypes.c_float, c_p, c_p, c_sz, c_p], c_i32),
+    # _PACKED: the packed layer, then q ... out, workspace, workspace bytes, stream
+    "rtkv_decode_attention_packed": (_PACKED + [c_p, c_i64, c_f, c_p, c_p, c_sz, c_p], c_i32),
     "rtkv_decode_tail_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
-    "rtkv_decode_attention_packed_tail": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64,
-                                           c_i32, c_p, c_p, c_i64, ctypes.c_float, c_p, c_p, c_p, c_sz, c_p], c_i32),
+    "rtkv_decode_attention_packed_tail": (_PACKED + [c_p, c_i64, c_f, c_p, c_p, c_p, c_sz, c_p], c_i32),
     "rtkv_extend_workspace_size": ([c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64], c_sz),
-    "rtkv_extend_attention_packed_tail": ([c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64,
-                                           c_i32, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_float, c_p, c_p,
-                                           c_p, c_sz, c_p], c_i32),
+    "rtkv_extend_attention_packed_tail": (_PACKED + [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p, c_sz,
+                                                     c_p], c_i32),
 }
 EXPORTS = tuple(_SIGS)
 

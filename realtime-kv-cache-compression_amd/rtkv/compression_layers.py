@@ -328,6 +328,55 @@ def unpack_layer(p: dict):
     return outs[0], outs[1]
 
 
+def _packed_args(where: str, p: dict, q: torch.Tensor, B: int, D: int, num_kv_heads: int, dev, nullable: bool):
+    """The packed layer dict `p` checked against a query (q's dtype, B batch rows, num_kv_heads heads of
+    D) and marshalled as the 15 leading arguments of the attention entry points.  Returns (args, Sp,
+    keep): Sp the layer's row capacity, keep the tensors the pointers belong to (the caller holds it across the
+    call).  nullable: a layer without row capacity passes null pointers (the tail forms)."""
+    if q.dtype != p["dtype"]:
+        raise ValueError(f"q dtype {q.dtype} does not match the packed layer's {p['dtype']}")
+    F = int(p["feature_dim"])
+    if num_kv_heads * D != F:
+        raise ValueError(f"num_kv_heads * head_dim = {num_kv_heads * D} != feature_dim {F}")
+    codes_k, codes_v = p["codes_k"], p["codes_v"]
+    row_offset = p["row_offset"].contiguous()
+    scale_zp = p["scale_zp"].contiguous()
+    kept_index = p["kept_index"].contiguous()
+    labels = p["labels"].contiguous()
+    _check_dtypes(where, p)
+    # the kernels index every per-batch array by q's batch row: they must all have B rows
+    if kept_index.dim() != 2 or kept_index.shape[0] != B or len(p["rows"]) != B or labels.shape[0] != B \
+            or row_offset.shape[0] != B or scale_zp.shape[0] != B:
+        raise ValueError(f"q has {B} batch rows but the packed layer has {kept_index.shape[0]} "
+                         f"(rows {len(p['rows'])}, labels {labels.shape[0]})")
+    Sp = kept_index.shape[1]
+    if row_offset.shape != (B, Sp) or scale_zp.shape != (B, Sp, 4):
+        raise ValueError("packed layer: row_offset / scale_zp shapes disagree with kept_index")
+    if codes_k.numel() != codes_v.numel():
+        raise ValueError("codes_k and codes_v differ in size")
+    if any(int(r) < 0 or int(r) > Sp for r in p["rows"]):
+        raise ValueError(f"row counts {p['rows']} outside [0, {Sp}]")
+    rows = p.get("_rows_dev")
+    if rows is None or rows.device != dev:  # kept once per layer: no host→device copy per decode step
+        rows = p["_rows_dev"] = torch.tensor(p["rows"], dtype=torch.int64, device=dev)
+    keep = (codes_k, codes_v, row_offset, scale_zp, kept_index, labels, rows)
+    pk = (lambda t: 0) if nullable and Sp == 0 else (lambda t: t.data_ptr())
+    args = (pk(codes_k), pk(codes_v), codes_k.numel(), pk(row_offset), pk(scale_zp), pk(kept_index), pk(labels), B,
+            labels.shape[1], Sp, pk(rows), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype], (ctypes.c_int32 * 3)(*p["bits"]))
+    return args, Sp, keep
+
+
+def _dense_tail(tail: "DecodeTail", q: torch.Tensor, B: int, F: int) -> "L.DenseTail":
+    """rtkv_dense_tail of `tail`, checked against q's batch, dtype and device and the feature_dim."""
+    if tail.k.dtype != q.dtype or tail.k.shape[0] != B or tail.k.shape[2] != F or tail.k.device != q.device \
+            or tail.v.shape != tail.k.shape or tail.rows_dev.shape != (B,) or tail.rows_dev.dtype != torch.int64:
+        raise ValueError(f"tail [{tuple(tail.k.shape)} {tail.k.dtype}] does not match q's batch {B}, feature_dim {F}, "
+                         f"dtype {q.dtype}")
+    cap = tail.capacity
+    return L.DenseTail(L.ptr(tail.k) if cap else 0, L.ptr(tail.v) if cap else 0, tail.rows_dev.data_ptr(), cap,
+                       tail.k.stride(0), tail.k.stride(1))
+
+
 def decode_attention(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optional[float] = None,
                      tail: Optional[DecodeTail] = None) -> torch.Tensor:
     """Attention of one new token per batch row over a packed layer, decoded on the fly
@@ -337,102 +386,35 @@ def decode_attention(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optiona
     (modified_llama.py:89).  tail: the dense rows of the tokens generated since (DecodeTail); the
     softmax then runs over the kept rows followed by the tail's rows, what a decode step of the
     reference attends over (modified_llama.py:83-94, 152; rtkv_decode_attention_packed_tail)."""
-    codes_k, codes_v = p["codes_k"], p["codes_v"]
     if tail is not None:
         return _decode_attention_tail(p, q, num_kv_heads, scale, tail)
-    L.require_device(codes_k, codes_v, q)
-    dev = codes_k.device
-    if q.dtype != p["dtype"]:
-        raise ValueError(f"q dtype {q.dtype} does not match the packed layer's {p['dtype']}")
+    L.require_device(p["codes_k"], p["codes_v"], q)
+    dev = p["codes_k"].device
     B, Hq, D = q.shape
-    F = int(p["feature_dim"])
-    if num_kv_heads * D != F:
-        raise ValueError(f"num_kv_heads * head_dim = {num_kv_heads * D} != feature_dim {F}")
-    row_offset = p["row_offset"].contiguous()
-    scale_zp = p["scale_zp"].contiguous()
-    kept_index = p["kept_index"].contiguous()
-    labels = p["labels"].contiguous()
-    _check_dtypes("decode", p)
-    # the kernel indexes every per-batch array by q's batch row: they must all have B rows
-    if kept_index.dim() != 2 or kept_index.shape[0] != B or len(p["rows"]) != B or labels.shape[0] != B \
-            or row_offset.shape[0] != B or scale_zp.shape[0] != B:
-        raise ValueError(f"q has {B} batch rows but the packed layer has {kept_index.shape[0]} "
-                         f"(rows {len(p['rows'])}, labels {labels.shape[0]})")
-    Sp = kept_index.shape[1]
-    if row_offset.shape != (B, Sp) or scale_zp.shape != (B, Sp, 4):
-        raise ValueError("packed layer: row_offset / scale_zp shapes disagree with kept_index")
-    S = labels.shape[1]
+    args, Sp, _keep = _packed_args("decode", p, q, B, D, num_kv_heads, dev, nullable=False)
     out = torch.zeros(B, Hq, D, dtype=torch.float32, device=dev)
     if Sp == 0:
         return out
-    rows = p.get("_rows_dev")
-    if rows is None or rows.device != dev:  # kept once per layer: no host→device copy per decode step
-        rows = p["_rows_dev"] = torch.tensor(p["rows"], dtype=torch.int64, device=dev)
-    bits = (ctypes.c_int32 * 3)(*p["bits"])
     qc = q.contiguous()
     ws = torch.empty(L.lib().rtkv_decode_workspace_size(B, Hq, num_kv_heads, D, Sp), dtype=torch.uint8, device=dev)
     sc = float(scale) if scale is not None else 1.0 / float(D) ** 0.5
-    if codes_k.numel() != codes_v.numel():
-        raise ValueError("codes_k and codes_v differ in size")
-    if any(int(r) < 0 or int(r) > Sp for r in p["rows"]):
-        raise ValueError(f"row counts {p['rows']} outside [0, {Sp}]")
-    L.check(L.lib().rtkv_decode_attention_packed(codes_k.data_ptr(), codes_v.data_ptr(), codes_k.numel(),
-                                                 row_offset.data_ptr(),
-                                                 scale_zp.data_ptr(), kept_index.data_ptr(), labels.data_ptr(), B, S,
-                                                 Sp, rows.data_ptr(), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype],
-                                                 bits, qc.data_ptr(), Hq, sc, out.data_ptr(), ws.data_ptr(),
+    L.check(L.lib().rtkv_decode_attention_packed(*args, qc.data_ptr(), Hq, sc, out.data_ptr(), ws.data_ptr(),
                                                  ws.numel(), L.stream_ptr(dev)), "rtkv_decode_attention_packed")
     return out
 
 
 def _decode_attention_tail(p: dict, q: torch.Tensor, num_kv_heads: int, scale: Optional[float], tail: DecodeTail):
-    codes_k, codes_v = p["codes_k"], p["codes_v"]
-    L.require_device(codes_k, codes_v, q, tail.k, tail.v, tail.rows_dev)
+    L.require_device(p["codes_k"], p["codes_v"], q, tail.k, tail.v, tail.rows_dev)
     dev = q.device
-    if q.dtype != p["dtype"]:
-        raise ValueError(f"q dtype {q.dtype} does not match the packed layer's {p['dtype']}")
     B, Hq, D = q.shape
-    F = int(p["feature_dim"])
-    if num_kv_heads * D != F:
-        raise ValueError(f"num_kv_heads * head_dim = {num_kv_heads * D} != feature_dim {F}")
-    if tail.k.dtype != q.dtype or tail.k.shape[0] != B or tail.k.shape[2] != F or tail.k.device != dev \
-            or tail.v.shape != tail.k.shape or tail.rows_dev.shape != (B,) or tail.rows_dev.dtype != torch.int64:
-        raise ValueError(f"tail [{tuple(tail.k.shape)} {tail.k.dtype}] does not match q's batch {B}, feature_dim {F}, "
-                         f"dtype {q.dtype}")
-    row_offset = p["row_offset"].contiguous()
-    scale_zp = p["scale_zp"].contiguous()
-    kept_index = p["kept_index"].contiguous()
-    labels = p["labels"].contiguous()
-    _check_dtypes("decode", p)
-    if kept_index.dim() != 2 or kept_index.shape[0] != B or len(p["rows"]) != B or labels.shape[0] != B \
-            or row_offset.shape[0] != B or scale_zp.shape[0] != B:
-        raise ValueError(f"q has {B} batch rows but the packed layer has {kept_index.shape[0]} "
-                         f"(rows {len(p['rows'])}, labels {labels.shape[0]})")
-    Sp = kept_index.shape[1]
-    if row_offset.shape != (B, Sp) or scale_zp.shape != (B, Sp, 4):
-        raise ValueError("packed layer: row_offset / scale_zp shapes disagree with kept_index")
-    if codes_k.numel() != codes_v.numel():
-        raise ValueError("codes_k and codes_v differ in size")
-    if any(int(r) < 0 or int(r) > Sp for r in p["rows"]):
-        raise ValueError(f"row counts {p['rows']} outside [0, {Sp}]")
-    S = labels.shape[1]
-    rows = p.get("_rows_dev")
-    if rows is None or rows.device != dev:
-        rows = p["_rows_dev"] = torch.tensor(p["rows"], dtype=torch.int64, device=dev)
+    args, Sp, _keep = _packed_args("decode", p, q, B, D, num_kv_heads, dev, nullable=True)
+    dt = _dense_tail(tail, q, B, num_kv_heads * D)
     out = torch.zeros(B, Hq, D, dtype=torch.float32, device=dev)
-    bits = (ctypes.c_int32 * 3)(*p["bits"])
     qc = q.contiguous()
-    cap = tail.capacity
-    dt = L.DenseTail(L.ptr(tail.k) if cap else 0, L.ptr(tail.v) if cap else 0, tail.rows_dev.data_ptr(), cap,
-                     tail.k.stride(0), tail.k.stride(1))
-    ws = torch.empty(L.lib().rtkv_decode_tail_workspace_size(B, Hq, num_kv_heads, D, Sp, cap), dtype=torch.uint8,
-                     device=dev)
+    ws = torch.empty(L.lib().rtkv_decode_tail_workspace_size(B, Hq, num_kv_heads, D, Sp, tail.capacity),
+                     dtype=torch.uint8, device=dev)
     sc = float(scale) if scale is not None else 1.0 / float(D) ** 0.5
-    pk = (lambda t: t.data_ptr()) if Sp else (lambda t: 0)  # no packed row capacity: null packed pointers
-    L.check(L.lib().rtkv_decode_attention_packed_tail(pk(codes_k), pk(codes_v), codes_k.numel(), pk(row_offset),
-                                                      pk(scale_zp), pk(kept_index), pk(labels), B, S, Sp,
-                                                      pk(rows), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype], bits,
-                                                      qc.data_ptr(), Hq, sc, ctypes.byref(dt), out.data_ptr(),
+    L.check(L.lib().rtkv_decode_attention_packed_tail(*args, qc.data_ptr(), Hq, sc, ctypes.byref(dt), out.data_ptr(),
                                                       ws.data_ptr(), ws.numel(), L.stream_ptr(dev)),
             "rtkv_decode_attention_packed_tail")
     return out
@@ -451,25 +433,15 @@ def extend_attention(p: dict, q: torch.Tensor, num_kv_heads: int, tail: DecodeTa
     (float32 states, other head dims) is computed with no new kernel: T single-token steps of
     decode_attention(..., tail=) over the same buffers with device-side counts n_b − (T−1−t) clamped
     at 0 — the same result, at the cost of T decode steps."""
-    codes_k, codes_v = p["codes_k"], p["codes_v"]
-    L.require_device(codes_k, codes_v, q, tail.k, tail.v, tail.rows_dev)
+    L.require_device(p["codes_k"], p["codes_v"], q, tail.k, tail.v, tail.rows_dev)
     dev = q.device
     if q.dim() != 4:
         raise ValueError(f"q must be [B, Hq, T, D], got {tuple(q.shape)}")
-    if q.dtype != p["dtype"]:
-        raise ValueError(f"q dtype {q.dtype} does not match the packed layer's {p['dtype']}")
     B, Hq, T, D = q.shape
-    F = int(p["feature_dim"])
     if T < 1:
         raise ValueError("q holds no new token (T < 1)")
-    if num_kv_heads * D != F:
-        raise ValueError(f"num_kv_heads * head_dim = {num_kv_heads * D} != feature_dim {F}")
     if num_kv_heads < 1 or Hq % num_kv_heads:
         raise ValueError(f"{Hq} query heads are not a multiple of {num_kv_heads} kv heads")
-    if tail.k.dtype != q.dtype or tail.k.shape[0] != B or tail.k.shape[2] != F or tail.k.device != dev \
-            or tail.v.shape != tail.k.shape or tail.rows_dev.shape != (B,) or tail.rows_dev.dtype != torch.int64:
-        raise ValueError(f"tail [{tuple(tail.k.shape)} {tail.k.dtype}] does not match q's batch {B}, feature_dim {F}, "
-                         f"dtype {q.dtype}")
     if q.dtype not in (torch.float16, torch.bfloat16) or D != 128:
         # outside the kernel's envelope: T decode steps, step t seeing the tail up to its own token
         out = torch.empty(B, Hq, T, D, dtype=torch.float32, device=dev)
@@ -479,44 +451,17 @@ def extend_attention(p: dict, q: torch.Tensor, num_kv_heads: int, tail: DecodeTa
             out[:, :, t] = _decode_attention_tail(p, q[:, :, t], num_kv_heads, scale,
                                                   DecodeTail.from_tensors(tail.k, tail.v, rows_t))
         return out
-    row_offset = p["row_offset"].contiguous()
-    scale_zp = p["scale_zp"].contiguous()
-    kept_index = p["kept_index"].contiguous()
-    labels = p["labels"].contiguous()
-    _check_dtypes("extend", p)
-    if kept_index.dim() != 2 or kept_index.shape[0] != B or len(p["rows"]) != B or labels.shape[0] != B \
-            or row_offset.shape[0] != B or scale_zp.shape[0] != B:
-        raise ValueError(f"q has {B} batch rows but the packed layer has {kept_index.shape[0]} "
-                         f"(rows {len(p['rows'])}, labels {labels.shape[0]})")
-    Sp = kept_index.shape[1]
-    if row_offset.shape != (B, Sp) or scale_zp.shape != (B, Sp, 4):
-        raise ValueError("packed layer: row_offset / scale_zp shapes disagree with kept_index")
-    if codes_k.numel() != codes_v.numel():
-        raise ValueError("codes_k and codes_v differ in size")
-    if any(int(r) < 0 or int(r) > Sp for r in p["rows"]):
-        raise ValueError(f"row counts {p['rows']} outside [0, {Sp}]")
-    S = labels.shape[1]
-    rows = p.get("_rows_dev")
-    if rows is None or rows.device != dev:
-        rows = p["_rows_dev"] = torch.tensor(p["rows"], dtype=torch.int64, device=dev)
+    args, Sp, _keep = _packed_args("extend", p, q, B, D, num_kv_heads, dev, nullable=True)
+    dt = _dense_tail(tail, q, B, num_kv_heads * D)
     if q.stride(3) != 1 or any(st % 8 for st in q.stride()[:3]) or q.data_ptr() % 16:
         q = q.contiguous()
     out = torch.empty(B, Hq, T, D, dtype=torch.float32, device=dev)
-    bits = (ctypes.c_int32 * 3)(*p["bits"])
-    cap = tail.capacity
-    dt = L.DenseTail(L.ptr(tail.k) if cap else 0, L.ptr(tail.v) if cap else 0, tail.rows_dev.data_ptr(), cap,
-                     tail.k.stride(0), tail.k.stride(1))
-    ws = torch.empty(L.lib().rtkv_extend_workspace_size(B, Hq, num_kv_heads, D, T, Sp, cap), dtype=torch.uint8,
+    ws = torch.empty(L.lib().rtkv_extend_workspace_size(B, Hq, num_kv_heads, D, T, Sp, tail.capacity), dtype=torch.uint8,
                      device=dev)
     sc = float(scale) if scale is not None else 1.0 / float(D) ** 0.5
-    pk = (lambda t: t.data_ptr()) if Sp else (lambda t: 0)  # no packed row capacity: null packed pointers
-    L.check(L.lib().rtkv_extend_attention_packed_tail(pk(codes_k), pk(codes_v), codes_k.numel(), pk(row_offset),
-                                                      pk(scale_zp), pk(kept_index), pk(labels), B, S, Sp,
-                                                      pk(rows), num_kv_heads, D, L.TORCH_DTYPE_CODE[q.dtype], bits,
-                                                      q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), Hq, T, sc,
-                                                      ctypes.byref(dt), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      L.stream_ptr(dev)),
-            "rtkv_extend_attention_packed_tail")
+    L.check(L.lib().rtkv_extend_attention_packed_tail(*args, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), Hq, T,
+                                                      sc, ctypes.byref(dt), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      L.stream_ptr(dev)), "rtkv_extend_attention_packed_tail")
     return out
 
 

@@ -170,6 +170,39 @@ def test_batch_of_two_with_strided_tail():
     assert torch.equal(out[0], rtkv.decode_attention(pk, q, Hkv)[0])
 
 
+def test_more_than_64_splits_in_one_list():
+    """The packed and the tail splits are one list that the merge walks in 64 phases.  A packed row
+    capacity of 2560 gives ceil(2560 / 64) = 40 packed splits and a tail capacity of 1920 gives
+    ceil(1920 / 64) = 30 tail splits (both under the 1024-workgroup target: B·GS·HG = 1; the tuning
+    knob RTKV_DECODE_WGS is taken as unset), 70 in all: merge phases 0 to 5 take two splits each
+    (s and s + 64, the latter tail splits 24 to 29), phases 6 to 63 one.  The tail holds 100 rows, so
+    a tail split owns ceil(100 / 30) = 4 rows: tail splits 0 to 24 have rows, 25 to 29 are empty
+    (m = -inf) — and those are splits 65 to 69 of the list, the second ones of phases 1 to 5."""
+    import rtkv
+    import rtkv._lib as L
+    S, Hkv, D, Hq, dtype = 700, 4, 128, 4, "float16"
+    F, cap, tcap, T = Hkv * D, 2560, 1920, 100
+    k2, v2, pk0 = layer(1, S, Hkv, D, dtype)
+    n0 = pk0["kept_index"].shape[1]
+    assert 0 < n0 <= cap
+    pk = {k: v for k, v in pk0.items() if k != "_rows_dev"}
+    for name in ("row_offset", "scale_zp", "kept_index"):       # the same rows in a layer of capacity 2560
+        t = pk0[name]
+        pk[name] = torch.cat([t, torch.zeros(1, cap - n0, *t.shape[2:], dtype=t.dtype, device=t.device)], 1)
+    # 40 and 30 splits of (2·Hkv + F) floats, as rtkv_decode_tail_workspace_size lays them out
+    part = (2 * Hkv + F) * 4
+    assert L.lib().rtkv_decode_tail_workspace_size(1, Hq, Hkv, D, cap, tcap) \
+        == (40 * part + 256 + 255) // 256 * 256 + 30 * part + 256
+    q = rand(71, (1, Hq, D), dtype)
+    tk, tv = make_tail(72, 1, T, F, dtype, spare=tcap - T)
+    out = rtkv.decode_attention(pk, q, Hkv, tail=rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([T])))
+    ref = reference(k2, v2, pk["rows"], tk, tv, [T], q, Hkv, 1.0 / D ** 0.5)
+    check(out, ref, v2, tv, [T])
+    # no tail row: every tail split is empty, the bits of the packed-only step
+    none = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([0]))
+    assert torch.equal(rtkv.decode_attention(pk, q, Hkv, tail=none), rtkv.decode_attention(pk, q, Hkv))
+
+
 def empty_packed(B, F, dtype):
     z = lambda *s, dt: torch.zeros(*s, dtype=dt, device="cuda")  # noqa: E731
     return {"codes_k": z(0, dt=torch.uint8), "codes_v": z(0, dt=torch.uint8), "row_offset": z(B, 0, dt=torch.int64),
