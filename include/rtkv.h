@@ -689,6 +689,35 @@ int rtkv_gq_decode_attention(const rtkv_kv_desc* kv, const int32_t* kept_index_d
                              const void* raw_dev, int64_t row_capacity, const void* q_dev, int64_t Hq, float scale,
                              float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Generation on a gq layer: one decode step over the layer's gq rows followed by a dense tail of new
+ * tokens.  The format has NO REFERENCE COUNTERPART; the step reproduces, for a gq layer, the keys of the
+ * reference's decode step (modified_llama.py:83-94, 152: the new token's K/V are concatenated onto the
+ * cache and attention runs over all of it).  out[h,:] (fp32 [Hq, 128]) is one softmax over the first
+ * min(stats->kept, row_capacity) gq rows — K'/V' decoded from the codes to exactly the values
+ * rtkv_gq_unpack writes, outlier channels included, K and V with their own outlier lists — followed by
+ * the tail's clamp(tail->rows_dev[0], 0, tail->capacity) rows as stored (rtkv_dense_tail, B = 1).
+ * Stream-ordered, no host synchronisation; nothing at or past either count is read; zeros where both
+ * counts are 0; a kept count of 0 on the device means attention over the tail alone.  A row whose kept
+ * index is outside [0, S), whose offset is negative or whose codes would pass codes_capacity is skipped.
+ * The arguments through `scale` are those of rtkv_gq_decode_attention, in the same order and with the
+ * same meaning (kv: shapes and dtype only, its pointers are not read); row_capacity == 0 is allowed
+ * (tail only; the layer's pointers may then be null).  All three dtypes; any Hq that is a multiple of
+ * Hkv.  The gq rows and the tail are split with the decode family's rule (from row_capacity and
+ * tail->capacity) into one list of partials that one merge takes.  Workspace (4-byte aligned):
+ * rtkv_gq_decode_tail_workspace_size(Hq, Hkv, row_capacity, tail->capacity) bytes, non-decreasing in
+ * both capacities.  RTKV_ERR_INVALID ("gq decode: ..."), checked on the host before any launch: B != 1,
+ * head_dim != 128, heads not contiguous, H not a multiple of 4 up to 64, class widths other than 2/4/8,
+ * Hq not a multiple of Hkv, a null or misaligned q, out, tail struct, tail base or tail stride,
+ * tail stride_s < Hkv*128, a negative capacity, a null rows_dev, a too-small workspace. */
+size_t rtkv_gq_decode_tail_workspace_size(int64_t Hq, int64_t Hkv, int64_t row_capacity, int64_t tail_capacity);
+int rtkv_gq_decode_attention_tail(const rtkv_kv_desc* kv, const int32_t* kept_index_dev, const uint8_t* labels_dev,
+                                  const rtkv_layer_stats* stats_dev, const int32_t bits[3], const rtkv_gq_params* g,
+                                  const int16_t* outlier_idx_dev, const int64_t* row_offset_dev,
+                                  const uint8_t* codes_k_dev, const uint8_t* codes_v_dev, int64_t codes_capacity,
+                                  const void* meta_dev, const void* raw_dev, int64_t row_capacity, const void* q_dev,
+                                  int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Copy the kept rows of a row-major tensor (row r of batch b = src row kept_index[b*cap + r]), zero
  * rows for r in [kept_b, S'_max), rows of row_bytes bytes, into dst (batch stride dst_stride_b bytes,
  * or S'_max*row_bytes when -1).  The pure gather of apply_token_selection (selective_propagation.py

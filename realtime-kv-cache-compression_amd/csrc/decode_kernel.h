@@ -66,6 +66,10 @@ inline DecodeParts decode_parts(void* ws, int64_t B, int64_t G, int64_t Hkv, int
 // write splits 0 .. decode_splits(cap) − 1 of `parts`.
 int launch_decode_splits(const PackedLayer& p, const void* q, int64_t Hq, float scale, const DecodeParts& parts,
                          hipStream_t st);
+// The dense tail's half (decode_tail.hip): the tail kernel over the (checked) tail's rows writes splits
+// first .. first + decode_splits(tail->capacity) − 1 of `parts`.
+int launch_tail_splits(const rtkv_dense_tail* tail, int dt, int64_t B, int64_t Hkv, int64_t D, const void* q, int64_t Hq,
+                       float scale, const DecodeParts& parts, int first, hipStream_t st);
 // out[b, hq, d] from the n splits of `parts` (decode.hip)
 int launch_decode_merge(const DecodeParts& parts, int64_t B, int64_t Hq, int64_t Hkv, int64_t D, float* out,
                         hipStream_t st);

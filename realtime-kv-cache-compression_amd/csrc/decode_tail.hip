@@ -240,6 +240,34 @@ size_t decode_tail_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t D
   return packed + (size_t)(B * G) * st * (size_t)(2 * Hkv + Hkv * D) * sizeof(float) + 256;
 }
 
+// The tail half of a decode step: the tail's decode_splits(tail->capacity) splits are written as splits
+// first .. of `parts` (the list of the whole step; the caller has checked the tail and sized the list).
+int launch_tail_splits(const rtkv_dense_tail* tail, int dt, int64_t B, int64_t Hkv, int64_t D, const void* q, int64_t Hq,
+                       float scale, const DecodeParts& parts, int first, hipStream_t st) {
+  const int64_t F = Hkv * D, G = Hq / Hkv;
+  const DecodeShape sh = decode_shape(F, G);
+  TailArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.k = tail->k_dev; a.v = tail->v_dev; a.rows = tail->rows_dev;
+  a.cap = tail->capacity; a.stride_b = tail->stride_b; a.stride_s = tail->stride_s;
+  a.Hkv = (int)Hkv; a.D = (int)D; a.G = (int)G;
+  a.HG = sh.hg; a.GS = sh.gs;
+  a.q = q; a.scale = scale * 1.4426950408889634f;
+  a.splits = decode_splits(B, G, F, tail->capacity);
+  a.nrest = (int)((int64_t)a.splits * a.HG * B);
+  a.n = parts.n;  // the tail's splits follow the `first` ones before them
+  a.part_m = parts.m + (int64_t)first * Hkv;
+  a.part_l = parts.l + (int64_t)first * Hkv;
+  a.part_acc = parts.acc + (int64_t)first * F;
+  const int64_t nblk = ((int64_t)a.nrest + 7) / 8 * 8 * a.GS;
+  RTKV_REQUIRE(nblk < (1ll << 31), "decode: grid too large");
+  const dim3 grid((unsigned)nblk);
+  const size_t lds = (size_t)kDW * 64 * sh.nch * sh.gq * 10 * sizeof(float);
+  if (dt == RTKV_F16) return launch_tail_split<RTKV_F16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
+  if (dt == RTKV_BF16) return launch_tail_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
+  return launch_tail_split<RTKV_F32>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
+}
+
 int launch_decode_tail(PackedLayer& p, const void* q, int64_t Hq, float scale, const rtkv_dense_tail* tail, float* out,
                        void* ws, size_t ws_bytes, hipStream_t st) {
   const AttnChecks c = {"decode: ", RTKV_ERR_INVALID, 1u << RTKV_F32 | 1u << RTKV_F16 | 1u << RTKV_BF16, 0, 65535,
@@ -253,30 +281,9 @@ int launch_decode_tail(PackedLayer& p, const void* q, int64_t Hq, float scale, c
     return rc;
   if ((rc = check_packed_layer(c, p)) != RTKV_OK) return rc;
   const int sp = p.r.cap >= 1 ? decode_splits(B, G, F, p.r.cap) : 0;
-  const DecodeShape sh = decode_shape(F, G);
-  TailArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.k = tail->k_dev; a.v = tail->v_dev; a.rows = tail->rows_dev;
-  a.cap = tail->capacity; a.stride_b = tail->stride_b; a.stride_s = tail->stride_s;
-  a.Hkv = (int)Hkv; a.D = (int)D; a.G = (int)G;
-  a.HG = sh.hg; a.GS = sh.gs;
-  a.q = q; a.scale = scale * 1.4426950408889634f;
-  a.splits = decode_splits(B, G, F, tail->capacity);
-  a.nrest = (int)((int64_t)a.splits * a.HG * B);
-  const DecodeParts parts = decode_parts(ws, B, G, Hkv, sp + a.splits);
+  const DecodeParts parts = decode_parts(ws, B, G, Hkv, sp + decode_splits(B, G, F, tail->capacity));
   if (sp > 0 && (rc = launch_decode_splits(p, q, Hq, scale, parts, st)) != RTKV_OK) return rc;
-  a.n = parts.n;  // the tail's splits follow the sp packed ones
-  a.part_m = parts.m + (int64_t)sp * Hkv;
-  a.part_l = parts.l + (int64_t)sp * Hkv;
-  a.part_acc = parts.acc + (int64_t)sp * F;
-  const int64_t nblk = ((int64_t)a.nrest + 7) / 8 * 8 * a.GS;
-  RTKV_REQUIRE(nblk < (1ll << 31), "decode: grid too large");
-  const dim3 grid((unsigned)nblk);
-  const size_t lds = (size_t)kDW * 64 * sh.nch * sh.gq * 10 * sizeof(float);
-  if (p.dt == RTKV_F16) rc = launch_tail_split<RTKV_F16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  else if (p.dt == RTKV_BF16) rc = launch_tail_split<RTKV_BF16>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  else rc = launch_tail_split<RTKV_F32>(a, sh.nch, sh.gq, (int)D, grid, lds, st);
-  if (rc != RTKV_OK) return rc;
+  if ((rc = launch_tail_splits(tail, p.dt, B, Hkv, D, q, Hq, scale, parts, sp, st)) != RTKV_OK) return rc;
   return launch_decode_merge(parts, B, Hq, Hkv, D, out, st);
 }
 

@@ -149,6 +149,10 @@ _SIGS = {
     "rtkv_gq_decode_workspace_size": ([c_i64, c_i64], c_sz),
     "rtkv_gq_decode_attention": ([c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64,
                                   c_f, c_p, c_p, c_sz, c_p], c_i32),
+    "rtkv_gq_decode_tail_workspace_size": ([c_i64, c_i64, c_i64, c_i64], c_sz),
+    # rtkv_gq_decode_attention's arguments through scale, then tail, out, workspace, workspace bytes, stream
+    "rtkv_gq_decode_attention_tail": ([c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p,
+                                       c_i64, c_f, c_p, c_p, c_p, c_sz, c_p], c_i32),
     "rtkv_quantize_rows_shard": ([c_p, c_i64, c_i64, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p], c_i32),
     "rtkv_shard_ranges": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p, c_p], c_i32),
     "rtkv_importance_qk_lse": ([c_p, c_i32, c_p, c_p], c_i32),

@@ -33,6 +33,7 @@ class CompressedKVCache:
         self.cache_data: Dict[int, dict] = {}
         self.compression_info: Dict[int, dict] = {}
         self.tails: Dict[int, "DecodeTail"] = {}
+        self.gq: Dict[int, "GroupQuantKVCache"] = {}  # layers served from the rtkv-gq/1 format
 
     def store_compressed_kv(self, layer_idx: int, keys: torch.Tensor, values: torch.Tensor,
                             importance_scores: torch.Tensor, precision_labels: torch.Tensor,
@@ -53,26 +54,51 @@ class CompressedKVCache:
         self.cache_data.clear()
         self.compression_info.clear()
         self.tails.clear()
+        self.gq.clear()
 
     # ------------------------------------------------------------------ packed form (extension)
     def store_packed(self, layer_idx: int, packed: dict):
         """Keep only the packed codes of a layer (``info['packed']`` of compress_layer_kv_cache)."""
         self.compression_info[layer_idx] = packed
+        self.gq.pop(layer_idx, None)
         self.tails.pop(layer_idx, None)  # a new prefill: the tokens generated after the old one are gone
 
+    def store_group_quant(self, layer_idx: int, cache: "GroupQuantKVCache"):
+        """Serve a layer from the rtkv-gq/1 format (``info['group_quant']`` of compress_layer_kv_cache with
+        ``group_quant=``): append, tail_len, attend and attend_chunk then work on it as on a packed layer,
+        so CompressedDecodeAttention generates over it unchanged.  The format has no file form: save,
+        load, packed_nbytes and dequantize refuse such a layer (use cache.nbytes() / cache.dequantize())."""
+        from .group_quant import GroupQuantKVCache
+        if not isinstance(cache, GroupQuantKVCache):
+            raise ValueError("store_group_quant takes a GroupQuantKVCache (info['group_quant'])")
+        self.gq[layer_idx] = cache
+        self.compression_info.pop(layer_idx, None)
+        self.tails.pop(layer_idx, None)  # a new prefill: the tokens generated after the old one are gone
+
+    def _no_gq(self, layer_idx, what: str):
+        if layer_idx in self.gq:
+            raise ValueError(f"{what}: layer {layer_idx} is held in the rtkv-gq/1 format, which has no per-token "
+                             f"packed form and no file format (use the GroupQuantKVCache's own methods)")
+
     def packed_nbytes(self, layer_idx: int) -> int:
+        self._no_gq(layer_idx, "packed_nbytes")
         p = self.compression_info[layer_idx]
         return (p["codes_k"].numel() + p["codes_v"].numel() + p["scale_zp"].numel() * 4
                 + p["kept_index"].numel() * 4)
 
     def dequantize(self, layer_idx: int):
         """Decode a packed layer back to dense (K', V') [B, S'_max, F] on the device."""
+        self._no_gq(layer_idx, "dequantize")
         p = self.compression_info[layer_idx]
         return unpack_layer(p)
 
     def attend(self, layer_idx: int, q: torch.Tensor, num_kv_heads: int, scale: Optional[float] = None):
         """One decode step of attention over the packed layer (no dense K'/V'), followed by the
         layer's appended tokens when there are any: fp32 [B, Hq, D]."""
+        g = self.gq.get(layer_idx)
+        if g is not None:
+            _gq_heads(g, q, num_kv_heads)
+            return g.attend(q, scale, tail=self.tails.get(layer_idx))
         return decode_attention(self.compression_info[layer_idx], q, num_kv_heads, scale,
                                 tail=self.tails.get(layer_idx))
 
@@ -83,6 +109,9 @@ class CompressedKVCache:
         t = self.tails.get(layer_idx)
         if t is None:
             raise ValueError(f"layer {layer_idx} has no appended tokens: append the chunk's K/V first")
+        g = self.gq.get(layer_idx)
+        if g is not None:
+            return gq_extend_attention(g, q, num_kv_heads, t, scale)
         return extend_attention(self.compression_info[layer_idx], q, num_kv_heads, t, scale)
 
     def append(self, layer_idx: int, k_new: torch.Tensor, v_new: torch.Tensor):
@@ -91,7 +120,10 @@ class CompressedKVCache:
         decode step concatenates, it does not compress).  The layer's DecodeTail is created on first
         use with the packed layer's dtype, feature_dim and batch size."""
         t = self.tails.get(layer_idx)
-        if t is None:
+        if t is None and layer_idx in self.gq:
+            g = self.gq[layer_idx]
+            t = self.tails[layer_idx] = DecodeTail(1, g.F, g.dtype, g.device, capacity=self.tail_capacity)
+        elif t is None:
             p = self.compression_info[layer_idx]
             t = self.tails[layer_idx] = DecodeTail(p["kept_index"].shape[0], int(p["feature_dim"]), p["dtype"],
                                                    p["codes_k"].device, capacity=self.tail_capacity)
@@ -105,11 +137,15 @@ class CompressedKVCache:
     def save(self, path: str):
         """Write every packed layer to one safetensors file (see save_packed for the format).
         Appended tokens (the DecodeTails) are not serialized: the file holds the prefill only."""
+        for i in self.gq:
+            self._no_gq(i, "save")
         save_packed(self.compression_info, path)
 
     def load(self, path: str, device="cuda"):
         """Read the packed layers of a file written by save(); replaces the packed layers held and
         drops every tail (the file has none)."""
+        for i in self.gq:
+            self._no_gq(i, "load")
         self.compression_info = load_packed(path, device)
         self.tails.clear()
 
@@ -462,6 +498,34 @@ def extend_attention(p: dict, q: torch.Tensor, num_kv_heads: int, tail: DecodeTa
     L.check(L.lib().rtkv_extend_attention_packed_tail(*args, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), Hq, T,
                                                       sc, ctypes.byref(dt), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                       L.stream_ptr(dev)), "rtkv_extend_attention_packed_tail")
+    return out
+
+
+def _gq_heads(g, q: torch.Tensor, num_kv_heads: int):
+    if num_kv_heads != g.H:
+        raise ValueError(f"num_kv_heads {num_kv_heads} != the gq layer's {g.H} heads of 128")
+    if q.shape[0] != 1:
+        raise ValueError("a gq layer holds one batch row (B = 1)")
+
+
+def gq_extend_attention(g, q: torch.Tensor, num_kv_heads: int, tail: DecodeTail,
+                        scale: Optional[float] = None) -> torch.Tensor:
+    """extend_attention over a layer in the rtkv-gq/1 format (a GroupQuantKVCache): q [1, Hq, T, 128], the
+    tail already holding the T new tokens as its last T rows; fp32 [1, Hq, T, 128], query t over every
+    gq row and the tail rows u < max(0, n − (T−1−t)).  There is no multi-token gq kernel: T single-token
+    steps of g.attend(..., tail=) over the same buffers with device-side counts — the fall-back
+    extend_attention takes outside its kernel's envelope."""
+    if q.dim() != 4:
+        raise ValueError(f"q must be [1, Hq, T, 128], got {tuple(q.shape)}")
+    _gq_heads(g, q, num_kv_heads)
+    B, Hq, T, D = q.shape
+    if T < 1:
+        raise ValueError("q holds no new token (T < 1)")
+    out = torch.empty(B, Hq, T, D, dtype=torch.float32, device=q.device)
+    n_b = tail.rows_dev.clamp(0, tail.capacity)
+    for t in range(T):
+        rows_t = (n_b - (T - 1 - t)).clamp_(min=0)
+        out[:, :, t] = g.attend(q[:, :, t], scale, tail=DecodeTail.from_tensors(tail.k, tail.v, rows_t))
     return out
 
 

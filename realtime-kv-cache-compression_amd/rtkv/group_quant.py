@@ -136,11 +136,15 @@ class GroupQuantKVCache:
             outs.append(out)
         return outs[0], outs[1]
 
-    def attend(self, q: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+    def attend(self, q: torch.Tensor, scale: Optional[float] = None, tail=None) -> torch.Tensor:
         """Decode attention of one new token q [1, Hq, 128] (K/V dtype) over the layer, from the codes
-        (rtkv_gq_decode_attention): out [1, Hq, 128] fp32."""
+        (rtkv_gq_decode_attention): out [1, Hq, 128] fp32.  tail (a DecodeTail): the dense rows of the tokens
+        generated since; one softmax over the layer's rows followed by the tail's, what a decode step of
+        the reference attends over (modified_llama.py:83-94, 152; rtkv_gq_decode_attention_tail)."""
         if q.dim() != 3 or q.shape[0] != 1 or q.shape[2] != GQ_D or q.dtype != self.dtype:
             raise ValueError("gq attend: q must be [1, Hq, 128] in the K/V dtype")
+        if tail is not None:
+            return self._attend_tail(q, scale, tail)
         self.wait()
         q = q.contiguous()
         Hq = q.shape[1]
@@ -153,6 +157,30 @@ class GroupQuantKVCache:
                                                  self.raw.data_ptr(), max(self.rows, 1), q.data_ptr(), Hq, s,
                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr(self.device)),
                 "rtkv_gq_decode_attention")
+        return out
+
+    def _attend_tail(self, q: torch.Tensor, scale: Optional[float], tail) -> torch.Tensor:
+        from .compression_layers import _dense_tail
+        L.require_device(q, tail.k, tail.v, tail.rows_dev)
+        if q.device != self.device:
+            raise ValueError(f"gq attend: q is on {q.device}, the layer on {self.device}")
+        dt = _dense_tail(tail, q, 1, self.F)
+        self.wait()
+        q = q.contiguous()
+        Hq = q.shape[1]
+        if Hq % self.H:
+            raise ValueError(f"gq attend: {Hq} query heads are not a multiple of {self.H} kv heads")
+        out = torch.empty(1, Hq, GQ_D, dtype=torch.float32, device=self.device)
+        cap = max(self.rows, 1)  # the rows the meta / raw buffers hold
+        ws = torch.empty(int(L.lib().rtkv_gq_decode_tail_workspace_size(Hq, self.H, cap, tail.capacity)),
+                         dtype=torch.uint8, device=self.device)
+        kd, ki, lb, st, b3, p, oi, ro = self._common()
+        s = float(scale) if scale is not None else 1.0 / math.sqrt(GQ_D)
+        L.check(L.lib().rtkv_gq_decode_attention_tail(kd, ki, lb, st, b3, p, oi, ro, self.codes_k.data_ptr(),
+                                                      self.codes_v.data_ptr(), self.codes_k.numel(),
+                                                      self.meta.data_ptr(), self.raw.data_ptr(), cap, q.data_ptr(), Hq,
+                                                      s, ctypes.byref(dt), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      L.stream_ptr(self.device)), "rtkv_gq_decode_attention_tail")
         return out
 
 

@@ -13,7 +13,14 @@ rows and a tail of `older` + T rows, next to the same work done as T single-toke
 rtkv_decode_attention_packed_tail (step t over the tail up to its own token), timed in the same run.
 `older` takes the values of --tail (default 0,1024).
 
-usage: decode_bench.py [cases e.g. 0,2] [iters] [--tail 0,128,1024,4096] [--chunk 1,4,16,64,256]"""
+--gq: the layer is also kept in the rtkv-gq/1 format (group_quant=, n_outlier 4).  For the same layer, in this
+process, in interleaved rounds (median and min..max over the rounds): the old gq kernel
+(rtkv_gq_decode_attention), the gq step with a dense tail (rtkv_gq_decode_attention_tail) for each --tail
+length (default 0,128,1024,4096), and the per-token step with the same tail
+(rtkv_decode_attention_packed_tail) over the per-token codes of the same kept rows, beside the bytes
+each format moves per row.
+
+usage: decode_bench.py [cases e.g. 0,2] [iters] [--tail 0,128,1024,4096] [--chunk 1,4,16,64,256] [--gq]"""
 import argparse
 import os
 import sys
@@ -89,6 +96,51 @@ def run_chunks(pk, q1, Hkv, Hq, D, chunks, olders, iters):
                   f"({us_1 / T:.1f} us/token) | ratio {us_1 / us:.2f}x", flush=True)
 
 
+def run_gq(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200, tails=(0, 128, 1024, 4096), rounds=5, n_outlier=4):
+    """The gq step (old kernel, new entry point with each tail) and the per-token step on the same kept rows,
+    interleaved: `rounds` rounds, each timing every variant for iters / rounds calls."""
+    F, e = Hkv * D, 2
+    K, V = synth.kv(11, 1, S, F, dtype)
+    W = synth.attention_slice(11, 1, 8, S, rtkv.prompt_length(S), dtype)
+    cfg = rtkv.CompressionConfig(num_hidden_layers=4, low_precision_bits=2, medium_precision_bits=4,
+                                 high_precision_bits=8, early_layer_ratio=ratio, middle_layer_ratio=ratio,
+                                 later_layer_ratio=ratio)
+    comp = rtkv.RealTimePrefillCompressor(cfg, group_quant=rtkv.GroupQuantConfig(n_outlier=n_outlier))
+    ids = torch.zeros(1, S, dtype=torch.long, device="cuda")
+    k2, v2, info = comp.compress_layer_kv_cache(dev(K, dtype), dev(V, dtype), dev(W, dtype), ids, 1)
+    pk, c = info["packed"], info["group_quant"]
+    n = int(pk["rows"][0])
+    q = torch.randn(1, Hq, D, device="cuda").to(TD[dtype])
+    tl = {}
+    for T in tails:
+        tl[T] = rtkv.DecodeTail(1, F, q.dtype, "cuda", capacity=max(T, 1))
+        if T:
+            tl[T].append(torch.randn(1, T, F, device="cuda").to(q.dtype), torch.randn(1, T, F, device="cuda").to(q.dtype))
+    variants = [("gq old kernel, no tail", lambda: c.attend(q))]
+    variants += [(f"gq tail T={T}", (lambda t: lambda: c.attend(q, tail=t))(tl[T])) for T in tails]
+    variants += [(f"per-token tail T={T}", (lambda t: lambda: rtkv.decode_attention(pk, q, Hkv, tail=t))(tl[T]))
+                 for T in tails]
+    us = {name: [] for name, _ in variants}
+    for _ in range(rounds):
+        for name, fn in variants:
+            us[name].append(timed(fn, max(10, iters // rounds)))
+    code = pk["codes_k"].numel() / max(n, 1)                        # mean code bytes per row and tensor
+    gq_row, tok_row = code + 2 * Hkv * e + Hkv * n_outlier * e, code + 8
+    print(f"S={S} Hkv={Hkv} Hq={Hq} {dtype} gq: kept {n}, n_outlier {n_outlier}; bytes per row and tensor: gq "
+          f"{gq_row:.0f} (codes {code:.0f} + meta {2 * Hkv * e} + raw {Hkv * n_outlier * e}), per-token {tok_row:.0f}: "
+          f"ratio {gq_row / tok_row:.3f}; {rounds} interleaved rounds of {max(10, iters // rounds)} calls", flush=True)
+    med = {name: float(np.median(v)) for name, v in us.items()}
+    for name, _ in variants:
+        v = us[name]
+        extra = ""
+        if name.startswith("gq tail"):
+            T = int(name.split("=")[1])
+            extra = f" | over the empty tail {med[name] - med[f'gq tail T={tails[0]}']:+.1f} us" if T != tails[0] else \
+                f" | old kernel / this {med['gq old kernel, no tail'] / med[name]:.2f}x"
+            extra += f" | this / per-token step {med[name] / med[f'per-token tail T={T}']:.2f}x"
+        print(f"    {name}: {med[name]:.1f} us (min {min(v):.1f}, max {max(v):.1f})" + extra, flush=True)
+
+
 def run(S, Hkv, Hq, dtype="float16", D=128, ratio=0.6, iters=200, tails=(), chunks=()):
     F = Hkv * D
     K, V = synth.kv(11, 1, S, F, dtype)
@@ -149,8 +201,13 @@ if __name__ == "__main__":
     ap.add_argument("iters", nargs="?", type=int, default=200)
     ap.add_argument("--tail", default="", help="comma-separated dense tail lengths, e.g. 0,128,1024,4096")
     ap.add_argument("--chunk", default="", help="comma-separated numbers of new tokens per multi-token step, e.g. 1,4,16,64,256")
+    ap.add_argument("--gq", action="store_true", help="the gq step (old kernel, new entry point with each tail) "
+                                                      "against the per-token step on the same rows")
     args = ap.parse_args()
     only = [int(x) for x in args.cases.split(",")] if args.cases else range(len(cases))
     tails = tuple(int(x) for x in args.tail.split(",")) if args.tail else ()
     for i in only:
+        if args.gq:
+            run_gq(*cases[i], iters=args.iters, tails=tails or (0, 128, 1024, 4096))
+            continue
         run(*cases[i], iters=args.iters, tails=tails, chunks=tuple(int(x) for x in args.chunk.split(",")) if args.chunk else ())
