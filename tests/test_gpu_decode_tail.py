@@ -9,19 +9,37 @@ sources are those of tests/test_gpu_decode.py — fp32 summation order and the h
 tolerance is that file's: rtol = 2e-4, atol = 2e-5 · max(max|V'|, max|tail V|, 1).
 
 Every unused tail row (capacity is always above the count) is filled with NaN: a finite output
-within tolerance shows that nothing at or past the count is read."""
+within tolerance shows that nothing at or past the count is read.
+
+Every layer keeps rows of all three precision classes (layer() asserts it), so each case decodes all
+three field widths.  The field of a class is one bit wider than its bits where 2^bits − 1 is not a value
+of the dtype (rtkv_field_width): bits (4, 8, 16) give the widths 4, 8 and 16 for float32, but 17 for
+bfloat16 — outside the widths 2/4/8/16 the attention kernels take — and float16 with 16 bits is outside
+what the quantizer accepts (tests/test_gpu_parity.py).  The 16-bit field of the two 16-bit dtypes is
+that of a 15-bit class: (4, 8, 15)."""
 import ctypes
+import math
 
 import numpy as np
 import pytest
 import torch
 
 import synth
+from attn_checks import check_onehot, onehot_tail, visible
 
 pytestmark = pytest.mark.gpu
 
 TD = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
-COV = dict(alpha=0.8, beta=0.1, gamma=0.1, theta_h=0.4, theta_m=0.25)
+# Class thresholds that split these layers' tokens about evenly (30 / 33 / 37 % high / medium / low), and
+# propagation ratios under which the budget runs out inside the lowest class: the high and the medium class are
+# kept whole, the low class in part, so the kept index is not the identity.  The cost of a row is its width:
+# with (2, 4, 8) a layer costs S · (high + medium / 2 + low / 4) ≈ 0.39 .. 0.59 · S, with (4, 8, 16) twice that.
+COV = dict(alpha=0.8, beta=0.1, gamma=0.1, theta_h=0.5, theta_m=0.4)
+RATIO = {620: 0.53, 800: 0.54, 650: 0.45}   # by S; every other S: 0.5.  (4, 8, 15) and (4, 8, 16): 1.0
+
+
+def default_ratio(S, bits):
+    return 1.0 if bits[2] >= 15 else RATIO.get(S, 0.5)
 TAILS = (1, 3, 5, 257, 1500)   # one row; fewer than the 4 waves; 5; past one 64-row round; several tail splits
 
 
@@ -46,8 +64,16 @@ def rand(seed, shape, dtype, mul=1.0):
 _LAYERS = {}
 
 
-def layer(B, S, Hkv, D, dtype, bits=(2, 4, 8), ratio=0.6):
-    """(K', V', packed) of one compressed synthetic layer, computed once per shape and left unchanged."""
+def kept_classes(pk, b=0):
+    """The precision class (0 low, 1 medium, 2 high) of each kept row of batch row b."""
+    n = int(pk["rows"][b])
+    return pk["labels"][b][pk["kept_index"][b, :n].long()].long()
+
+
+def layer(B, S, Hkv, D, dtype, bits=(2, 4, 8), ratio=None):
+    """(K', V', packed) of one compressed synthetic layer, computed once per shape and left unchanged.
+    All three classes are among the kept rows of every batch row."""
+    ratio = default_ratio(S, bits) if ratio is None else ratio
     key = (B, S, Hkv, D, dtype, bits, ratio)
     if key not in _LAYERS:
         import rtkv
@@ -61,7 +87,11 @@ def layer(B, S, Hkv, D, dtype, bits=(2, 4, 8), ratio=0.6):
         comp = rtkv.RealTimePrefillCompressor(cfg)
         ids = torch.zeros(B, S, dtype=torch.long, device="cuda")
         k2, v2, info = comp.compress_layer_kv_cache(dev(K, dtype), dev(V, dtype), dev(W, dtype), ids, 1)
-        _LAYERS[key] = (k2, v2, info["packed"])
+        pk = info["packed"]
+        for b in range(B):
+            counts = torch.bincount(kept_classes(pk, b), minlength=3)
+            assert (counts > 0).all() and int(pk["rows"][b]) < S, (key, b, counts.tolist())
+        _LAYERS[key] = (k2, v2, pk)
     return _LAYERS[key]
 
 
@@ -110,6 +140,7 @@ SHAPES = [
 ]
 CASES = [(s, dt, (2, 4, 8)) for s in SHAPES[:3] for dt in ("float16", "bfloat16", "float32")] \
     + [(s, "float32", (4, 8, 16)) for s in SHAPES[:3]] \
+    + [(s, dt, (4, 8, 15)) for s in SHAPES[:3] for dt in ("bfloat16", "float16")] \
     + [(s, "float16", (2, 4, 8)) for s in SHAPES[3:]]
 
 
@@ -152,7 +183,7 @@ def test_batch_of_two_with_strided_tail():
     import rtkv
     B, S, Hkv, D, Hq, dtype = 2, 800, 8, 128, 32, "float16"
     F = Hkv * D
-    k2, v2, pk0 = layer(B, S, Hkv, D, dtype, ratio=0.5)
+    k2, v2, pk0 = layer(B, S, Hkv, D, dtype)
     pk = {k: v for k, v in pk0.items() if k != "_rows_dev"}
     pk["rows"] = [int(pk0["rows"][0]), int(pk0["rows"][1]) - 17]   # the first rows of row 1's kept list
     cap = 9
@@ -259,6 +290,121 @@ def test_dominance_both_ways(dtype):
     out = rtkv.decode_attention(pk, q, Hkv, tail=tail)
     ref = reference(k2, v2, pk["rows"], tk, tv, [70], q, Hkv, 1.0 / D ** 0.5)
     check(out, ref, v2, tv, [70])
+
+
+def lead(X, q, D):
+    """(argmax, its lead in nats over every other row) of the scores q·Xᵀ/√D; X [N, D], q [D]."""
+    sc = X.double() @ q.double() / math.sqrt(D)
+    r = int(sc.argmax())
+    return r, (sc[r] - torch.cat([sc[:r], sc[r + 1:]]).max()).item() if sc.numel() > 1 else float("inf")
+
+
+def aimed_query(kh, r, D, dtype):
+    """A multiple of row r of kh [n, D] under which that row's score leads every other row of kh by 60 nats
+    (before the rounding to the dtype): c · kh[r], c = 60·√D / (|kh[r]|² − max_j kh[j]·kh[r])."""
+    dots = kh.double() @ kh[r].double()
+    gap = (dots[r] - torch.cat([dots[:r], dots[r + 1:]]).max()).item()
+    assert gap > 0, (r, gap)
+    return (kh[r].double() * (60.0 * math.sqrt(D) / gap)).to(TD[dtype])
+
+
+def single_rows(pk, b=0):
+    """The kept rows a single-row test aims at: the first row of each class, the last kept row (its width
+    comes from its class label, not from its byte span) and, where the layer has more than one split, the
+    first row of the second split of decode.hip (ceil(capacity / 64) splits) and of extend.hip (ceil(capacity
+    / 128)); both kernels give split s the rows [s · per, (s + 1) · per), per = ceil(rows / splits)."""
+    n, cap = int(pk["rows"][b]), pk["kept_index"].shape[1]
+    cls = kept_classes(pk, b)
+    rows = {f"first row of class {c}": int((cls == c).nonzero()[0]) for c in range(3)}
+    rows["last kept row"] = n - 1
+    for name, per_split in (("decode split 1", 64), ("extend split 1", 128)):
+        splits = -(-cap // per_split)
+        if splits > 1 and -(-n // splits) < n:
+            rows[name] = -(-n // splits)
+    return rows
+
+
+def swapped(pk):
+    """The layer with K and V exchanged (codes and scale / zero-point columns): its attention output is a
+    row of K', so the kernel's decode of the K codes is compared element for element as well."""
+    sw = {k: v for k, v in pk.items() if k != "_rows_dev"}
+    sw["codes_k"], sw["codes_v"] = pk["codes_v"], pk["codes_k"]
+    sw["scale_zp"] = pk["scale_zp"][..., [2, 3, 0, 1]].contiguous()
+    return sw
+
+
+SINGLE = [("float16", (2, 4, 8)), ("bfloat16", (2, 4, 8)), ("float16", (4, 8, 15)), ("bfloat16", (4, 8, 15)),
+          ("float32", (2, 4, 8)), ("float32", (4, 8, 16))]
+# Why rtol = 1e-5 and atol = 1e-8·vmax in the single-row tests: the test asserts that the row leads every
+# other visible row by more than 30 nats, so the others weigh less than N·e⁻³⁰ < 2100 · 9.4e-14 = 2e-10 together
+# and move the output by less than 4e-10·vmax; the row's own weight is exp2(0) = 1 (the running maximum is its
+# score), so what is left is a few fp32 roundings (1.2e-7 relative).  One ulp of a float16 value is 4.9e-4 of
+# it, of a bfloat16 value 3.9e-3: a dequantization that is one ulp off fails.
+SINGLE_RTOL, SINGLE_ATOL = 1e-5, 1e-8
+
+
+@pytest.mark.parametrize("dtype,bits", SINGLE, ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_one_packed_row_takes_the_whole_weight(dtype, bits):
+    """q of one query head a multiple of K'[r] of its kv head: the head's output is V'[r], for one row of
+    each class (each field width), the last kept row and the first row of a later split — and the same with
+    K and V exchanged, where the output is K'[r]."""
+    import rtkv
+    S, Hkv, D, Hq = 620, 4, 128, 8
+    F, G, T, hq = Hkv * D, Hq // Hkv, 5, 5
+    h = hq // G
+    k2, v2, pk = layer(1, S, Hkv, D, dtype, bits)
+    n = int(pk["rows"][0])
+    tk, tv = make_tail(202, 1, T, F, dtype)
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([T]))
+    for p, X, Y in ((pk, k2, v2), (swapped(pk), v2, k2)):
+        Xh = X[0, :n, h * D:(h + 1) * D]
+        vmax = max(Y[0, :n].float().abs().max().item(), tv[:, :T].float().abs().max().item(), 1.0)
+        for name, r in single_rows(pk).items():
+            q = rand(203, (1, Hq, D), dtype)
+            q[0, hq] = aimed_query(Xh, r, D, dtype)
+            top, by = lead(torch.cat([Xh, tk[0, :T, h * D:(h + 1) * D]]), q[0, hq], D)
+            assert top == r and by > 30, (name, r, top, by)
+            out = rtkv.decode_attention(p, q, Hkv, tail=tail)
+            row = Y[0, r, h * D:(h + 1) * D].float()
+            err = (out[0, hq] - row).abs().max().item()
+            print(f"{name} (row {r} of {n}, class {int(kept_classes(pk)[r])}): lead {by:.1f} nats, "
+                  f"max |out - row| {err:.2e}")
+            torch.testing.assert_close(out[0, hq], row, rtol=SINGLE_RTOL, atol=SINGLE_ATOL * vmax,
+                                       msg=lambda m: f"{name}: {m}")
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16", "float32"])
+def test_onehot_tail_map(dtype):
+    """Zero keys and one-hot values (attn_checks.onehot_tail) and no packed row: every weight is exactly 1,
+    so out[b, hq, c] = #{u < n : u mod D = c} / n with no tolerance — a tail row skipped or read twice shows
+    in its channel.  Counts around the 64-row round of the four waves and with several tail splits."""
+    import rtkv
+    Hkv, D, Hq = 4, 128, 8
+    k2, v2, pk0 = layer(1, 620, Hkv, D, dtype)
+    none = {k: v for k, v in pk0.items() if k != "_rows_dev"}
+    none["rows"] = [0]
+    q = rand(211, (1, Hq, D), dtype)
+    for n in (1, 3, 63, 64, 65, 257, 1500):
+        tk, tv = onehot_tail(1, n + 3, Hkv, D, TD[dtype], [n], "cuda")
+        tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n]))
+        for name, p in (("rows = [0]", none), ("no packed capacity", empty_packed(1, Hkv * D, dtype))):
+            check_onehot(rtkv.decode_attention(p, q, Hkv, tail=tail), torch.tensor([[n]]), f"{dtype} n = {n}, {name}")
+
+
+def test_17_bit_fields_are_refused():
+    """bfloat16 with a 16-bit class packs 17-bit fields (rtkv_field_width): both attention entry points refuse
+    the layer by name instead of reading it with another width."""
+    import rtkv
+    S, Hkv, D, Hq, dtype = 620, 4, 128, 8, "bfloat16"
+    k2, v2, pk = layer(1, S, Hkv, D, dtype, (4, 8, 16))
+    tk, tv = make_tail(221, 1, 4, Hkv * D, dtype)
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([4]))
+    for call in (lambda: rtkv.decode_attention(pk, rand(222, (1, Hq, D), dtype), Hkv),
+                 lambda: rtkv.decode_attention(pk, rand(222, (1, Hq, D), dtype), Hkv, tail=tail),
+                 lambda: rtkv.extend_attention(pk, rand(223, (1, Hq, 3, D), dtype), Hkv, tail)):
+        with pytest.raises(RuntimeError, match="field widths 2/4/8/16 only"):
+            call()
+    torch.cuda.synchronize()
 
 
 def test_count_above_capacity_is_clamped():

@@ -1,27 +1,40 @@
 """GPU: attention of T new tokens over a packed layer followed by the dense tail
-(rtkv_extend_attention_packed_tail, extend.hip) against plain PyTorch fp32 attention per (b, t) over
+(rtkv_extend_attention_packed_tail, extend.hip) against plain PyTorch float64 attention per (b, t) over
 cat(K'[:r_b], tail[:vis(b,t)]), vis(b,t) = max(0, n_b − (T−1−t)), K'/V' from compress_layer_kv_cache.
 The ground truth never comes from the code under test.
 
 Tolerance.  The error sources of tests/test_gpu_decode.py (fp32 summation order, hardware exp2) plus
-one: the softmax weights are rounded to the K/V dtype before the weights·V product on the matrix
-core (their sum stays fp32), which perturbs the output by at most u·max|V|, u = 2⁻¹¹ (float16) or
-2⁻⁸ (bfloat16).  So rtol = 2e-4, atol = (2e-5 + 2u)·vmax with vmax = max(max|V'|, max|tail V|, 1);
-the factor 2 covers float16 underflow of very small weights and the lazily trailing maximum.  The
-float32 fallback (single decode steps, no rounding of the weights) keeps the decode tests' 2e-5·vmax.
+one: the softmax weights pᵢ are rounded to the K/V dtype before the weights·V product on the matrix
+core (their sum stays fp32).  That moves output element d of a query by at most u·Σᵢ pᵢ|vᵢd| = u·A_d,
+u = 2⁻¹¹ (float16) or 2⁻⁸ (bfloat16), A = softmax(...)·|Y| the weighted mean of |V| in that channel under
+the same visibility mask.  So, elementwise (tests/attn_checks.py has the derivation and the reference),
+
+    |out − ref| ≤ 2e-4·|ref| + 2e-5·vmax + 2u·A,      vmax = max(max|V'|, max|tail V|, 1);
+
+the factor 2 covers float16 underflow of very small weights and the lazily trailing maximum.  A ≤ vmax,
+so this is nowhere looser than the (2e-5 + 2u)·vmax this file used before.  The float32 fallback (single
+decode steps, no rounding of the weights, u = 0) keeps the decode tests' 2e-5·vmax.  check() prints the
+worst |err| / bound of each comparison.  The largest seen on an MI355X: float16 0.30, bfloat16 0.35, both in
+test_tail_only's 70-token chunk, whose first queries see two or three keys, so that the roundings of their
+weights do not average out; the ground-truth cases stay at 0.06 (float16) and 0.07 (bfloat16), the CPU
+emulation of tests/test_attn_bound_host.py at 0.09 and 0.10; float32 0.001.
 
 Every unused tail row (capacity is always above the count) is NaN: a finite output within tolerance
-shows that nothing at or past a count is read."""
+shows that nothing at or past a count is read.
+
+The queries of the ground-truth cases carry a multiple of the keys at the two ends of what each query sees
+(attn_checks.plant_boundaries): without it a single row lost there is below the bfloat16 bound at about half of the steps."""
 import ctypes
 
 import pytest
 import torch
 
-from test_gpu_decode_tail import TD, empty_packed, layer, make_tail, rand
+from attn_checks import (QMUL, SHAPES, STEPS, Ref, check_bound, check_onehot, chunk_reference, onehot_tail,
+                         plant_boundaries, visible)
+from test_gpu_decode_tail import (SINGLE_ATOL, SINGLE_RTOL, TD, aimed_query, empty_packed, kept_classes, layer, lead,
+                                  make_tail, rand, single_rows, swapped)
 
 pytestmark = pytest.mark.gpu
-
-U = {"float16": 2.0 ** -11, "bfloat16": 2.0 ** -8, "float32": 0.0}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -32,72 +45,53 @@ def gpu():
     rtkv.build()
 
 
-def reference(k2, v2, rows, tk, tv, trows, q, Hkv, scale):
-    """fp32 softmax(q_t·Xᵀ·scale)·Y per (b, t): X/Y = cat(K'/V'[:rows[b]], tail[:vis(b, t)])."""
-    B, Hq, T, D = q.shape
-    G = Hq // Hkv
-    cap = tk.shape[1]
-    out = torch.zeros(B, Hq, T, D, dtype=torch.float32, device=q.device)
-    for b in range(B):
-        n, nb = int(rows[b]), min(max(int(trows[b]), 0), cap)
-        if n + nb == 0:
-            continue
-        Kf = torch.cat([k2[b, :n].float(), tk[b, :nb].float()]).view(n + nb, Hkv, D)
-        Vf = torch.cat([v2[b, :n].float(), tv[b, :nb].float()]).view(n + nb, Hkv, D)
-        s = torch.einsum("hgtd,nhd->hgtn", q[b].float().view(Hkv, G, T, D), Kf) * scale
-        vis = (nb - (T - 1 - torch.arange(T, device=q.device))).clamp(min=0)
-        seen = torch.arange(n + nb, device=q.device)[None, :] < (n + vis)[:, None]        # [T, n + nb]
-        p = torch.softmax(s.masked_fill(~seen, float("-inf")), dim=-1)
-        p = torch.where(seen.any(1)[:, None], p, torch.zeros_like(p))                     # no visible key: zeros
-        out[b] = torch.einsum("hgtn,nhd->hgtd", p, Vf).reshape(Hq, T, D)
-    return out
+reference = chunk_reference   # Ref(out, A) in float64 per (b, t), the counts clamped as the kernel clamps them
 
 
-def check(out, ref, v2, tv, trows, dtype):
-    assert torch.isfinite(out).all()
+def at(ref, *idx):
+    return Ref(ref.out[idx], ref.A[idx])
+
+
+def vmax_of(v2, tv, trows):
     cap = tv.shape[1]
     used = [min(max(int(t), 0), cap) for t in trows]
     tmax = max([tv[b, :t].float().abs().max().item() for b, t in enumerate(used) if t] + [0.0])
-    vmax = max(v2.float().abs().max().item() if v2.numel() else 0.0, tmax, 1.0)
-    atol = (2e-5 + 2 * U[dtype]) * vmax
-    err = (out - ref).abs().max().item()
-    print(f"max |err| {err:.3e}  atol {atol:.3e}  vmax {vmax:.3f}")
-    torch.testing.assert_close(out, ref, rtol=2e-4, atol=atol)
+    return max(v2.float().abs().max().item() if v2.numel() else 0.0, tmax, 1.0)
 
 
-SHAPES = [
-    # S, Hkv, D, Hq
-    (700, 4, 128, 4),        # G = 1
-    (900, 8, 128, 8),        # F = 1024
-    (620, 4, 128, 8),        # G = 2
-    (1000, 4, 128, 16),      # G = 4
-]
-# (T, older tail rows): T = 1, 2 the smallest steps; 5 below one 16-query MFMA group, 16 exactly one, 17 one
-# past; 70 past a pass of query rows.  Older rows: none, a few, past one 64-row round, several tail splits.
-STEPS = [
-    ((1, 0), (2, 3), (5, 257), (16, 1500), (17, 0), (70, 3)),
-    ((1, 1500), (2, 257), (5, 3), (16, 0), (17, 257), (70, 1500)),
-    ((1, 3), (2, 0), (5, 1500), (16, 257), (17, 3), (70, 0)),
-    ((1, 257), (2, 1500), (5, 0), (16, 3), (17, 1500), (70, 257)),
-]
-CASES = [(s, dt, STEPS[i]) for i, s in enumerate(SHAPES) for dt in ("float16", "bfloat16")]
+def check(out, ref, v2, tv, trows, dtype, what=""):
+    return check_bound(out, ref, vmax_of(v2, tv, trows), dtype, what)
 
 
-@pytest.mark.parametrize("shape,dtype,steps", CASES, ids=[f"{s[0]}-{s[1]}-{s[3]}-{dt}" for s, dt, _ in CASES])
-def test_ground_truth(shape, dtype, steps):
+# SHAPES and STEPS: attn_checks (tests/test_attn_bound_host.py runs the same ones on the CPU).  The 16-bit field
+# width (by_width<16>) is that of a 15-bit class: with 16 bits a bfloat16 layer packs 17-bit fields, which the
+# kernel refuses (test_gpu_decode_tail.test_17_bit_fields_are_refused), and a float16 layer is outside what the
+# quantizer accepts (tests/test_gpu_parity.py).
+CASES = [(s, dt, bits, STEPS[i]) for i, s in enumerate(SHAPES)
+         for dt, bits in (("float16", (2, 4, 8)), ("bfloat16", (2, 4, 8)), ("bfloat16", (4, 8, 15)),
+                          ("float16", (4, 8, 15)))]
+
+
+def case_id(s, dt, bits):
+    return f"{s[0]}-{s[1]}-{s[3]}-{dt}" + ("" if bits == (2, 4, 8) else "-" + "-".join(map(str, bits)))
+
+
+@pytest.mark.parametrize("shape,dtype,bits,steps", CASES, ids=[case_id(s, dt, b) for s, dt, b, _ in CASES])
+def test_ground_truth(shape, dtype, bits, steps):
     import rtkv
     S, Hkv, D, Hq = shape
     F = Hkv * D
-    k2, v2, pk = layer(1, S, Hkv, D, dtype, (2, 4, 8))
+    k2, v2, pk = layer(1, S, Hkv, D, dtype, bits)
     for T, older in steps:
         n = T + older
-        q = rand(S + T, (1, Hq, T, D), dtype)
+        q = rand(S + T, (1, Hq, T, D), dtype, QMUL)
         tk, tv = make_tail(S + 10 * n, 1, n, F, dtype)
+        q[0] = plant_boundaries(q[0], k2[0], int(pk["rows"][0]), tk[0], n, Hkv, TD[dtype])
         tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n]))
         out = rtkv.extend_attention(pk, q, Hkv, tail)
         assert out.shape == (1, Hq, T, D) and out.dtype == torch.float32
         ref = reference(k2, v2, pk["rows"], tk, tv, [n], q, Hkv, 1.0 / D ** 0.5)
-        check(out, ref, v2, tv, [n], dtype)
+        check(out, ref, v2, tv, [n], dtype, f"T {T} older {older}")
         assert torch.equal(rtkv.extend_attention(pk, q, Hkv, tail), out)   # deterministic
 
 
@@ -111,10 +105,11 @@ def test_agrees_with_single_steps(shape, dtype):
     q = rand(101, (1, Hq, T, D), dtype)
     tk, tv = make_tail(102, 1, n, Hkv * D, dtype)
     out = rtkv.extend_attention(pk, q, Hkv, rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n])))
+    A = reference(k2, v2, pk["rows"], tk, tv, [n], q, Hkv, 1.0 / D ** 0.5).A
     for t in range(T):
         one = rtkv.decode_attention(pk, q[:, :, t].contiguous(), Hkv,
                                     tail=rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n - (T - 1 - t)])))
-        check(out[:, :, t], one, v2, tv, [n], dtype)
+        check(out[:, :, t], Ref(one.double(), A[:, :, t]), v2, tv, [n], dtype, f"t {t}")
 
 
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
@@ -135,27 +130,27 @@ def test_no_causal_leak(dtype):
     out = rtkv.extend_attention(pk, q, Hkv, tail)
     ref = reference(k2, v2, pk["rows"], tk, tv, [n], q, Hkv, 1.0 / D ** 0.5)
     for t in (2, 3, 4):
-        check(out[:, :, t], ref[:, :, t], v2, tv, [n], dtype)
+        check(out[:, :, t], at(ref, slice(None), slice(None), t), v2, tv, [n], dtype, f"t {t}")
     check(out, ref, v2, tv, [n], dtype)
-    vmax = max(v2.float().abs().max().item(), tv[:, :n].float().abs().max().item(), 1.0)
-    atol = (2e-5 + 2 * U[dtype]) * vmax
     v3 = tv[0, older + 3, h * D:(h + 1) * D].float()
-    assert not torch.allclose(out[0, hq, 2], v3, rtol=2e-4, atol=atol)     # query 2 is not on token 3's value
+    assert (out[0, hq, 2] - v3).abs().max() > 0.5                          # query 2 is not on token 3's value
     # the other way: the key in query 2's own row
     tk, tv = make_tail(114, 1, n, F, dtype)
     tk[0, older + 2, h * D:(h + 1) * D] = q[0, hq, 2]
     tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n]))
     out = rtkv.extend_attention(pk, q, Hkv, tail)
     check(out, reference(k2, v2, pk["rows"], tk, tv, [n], q, Hkv, 1.0 / D ** 0.5), v2, tv, [n], dtype)
-    torch.testing.assert_close(out[0, hq, 2], tv[0, older + 2, h * D:(h + 1) * D].float(), rtol=2e-4, atol=atol)
+    own = tv[0, older + 2, h * D:(h + 1) * D].double()                     # the whole weight: A = |V| of that row
+    check(out[0, hq, 2], Ref(own, own.abs()), v2, tv, [n], dtype, "own row")
 
 
-def test_batch_of_two_with_strided_tail():
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
+def test_batch_of_two_with_strided_tail(dtype):
     """Different kept counts per row, tail counts [T, T + 7], a batch stride larger than capacity · F."""
     import rtkv
-    B, S, Hkv, D, Hq, dtype, T = 2, 800, 8, 128, 32, "float16", 6
+    B, S, Hkv, D, Hq, T = 2, 800, 8, 128, 32, 6
     F = Hkv * D
-    k2, v2, pk0 = layer(B, S, Hkv, D, dtype, ratio=0.5)
+    k2, v2, pk0 = layer(B, S, Hkv, D, dtype)
     pk = {k: v for k, v in pk0.items() if k != "_rows_dev"}
     pk["rows"] = [int(pk0["rows"][0]), int(pk0["rows"][1]) - 17]
     cap = T + 9
@@ -192,8 +187,8 @@ def test_tail_only(dtype):
         for p in (none, empty_packed(1, F, dtype)):
             out = rtkv.extend_attention(p, q, Hkv, tail)
             check(out, ref, v2[:, :0], tv, [T], dtype)
-            first = tv[0, 0].float().view(Hkv, 1, D).expand(Hkv, G, D).reshape(Hq, D)
-            torch.testing.assert_close(out[0, :, 0], first, rtol=2e-4, atol=(2e-5 + 2 * U[dtype]) * max(first.abs().max().item(), 1.0))
+            first = tv[0, 0].double().view(Hkv, 1, D).expand(Hkv, G, D).reshape(Hq, D)
+            check(out[0, :, 0], Ref(first, first.abs()), v2[:, :0], tv, [1], dtype, "query 0")
 
 
 def test_short_tail():
@@ -286,3 +281,89 @@ def test_module_loop():
     with pytest.raises(ValueError):
         chunk(q, k, v, attention_mask=torch.zeros(B, 1, 4, 4, device="cuda"))
     assert cache.tail_len(2) == 13
+
+
+@pytest.mark.parametrize("dtype,bits", [("float16", (2, 4, 8)), ("bfloat16", (2, 4, 8)), ("bfloat16", (4, 8, 15)),
+                                        ("float16", (4, 8, 15))],
+                         ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_one_packed_row_takes_the_whole_weight(dtype, bits):
+    """q of one (query head, t) a multiple of K'[r] of its kv head: that query's output is V'[r], for one row
+    of each class (each field width: by_width<2 / 4 / 8 / 16>), the last kept row (its width comes from its
+    label) and the first row of a later split — and the same with K and V exchanged, where the output is
+    K'[r].  The in-kernel decode (for float16 (h − zp)·sc in half arithmetic) is thereby compared element for
+    element with the K'/V' that compress_layer_kv_cache wrote.  Tolerance: test_gpu_decode_tail.SINGLE_RTOL."""
+    import rtkv
+    S, Hkv, D, Hq = 620, 4, 128, 8
+    F, G, T, older, hq, t = Hkv * D, Hq // Hkv, 5, 3, 5, 3
+    h, nt = hq // G, T + older
+    k2, v2, pk = layer(1, S, Hkv, D, dtype, bits)
+    n = int(pk["rows"][0])
+    tk, tv = make_tail(302, 1, nt, F, dtype)
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([nt]))
+    seen = int(visible(T, nt)[t])
+    for p, X, Y in ((pk, k2, v2), (swapped(pk), v2, k2)):
+        Xh = X[0, :n, h * D:(h + 1) * D]
+        vmax = max(Y[0, :n].float().abs().max().item(), tv[:, :nt].float().abs().max().item(), 1.0)
+        for name, r in single_rows(pk).items():
+            q = rand(303, (1, Hq, T, D), dtype)
+            q[0, hq, t] = aimed_query(Xh, r, D, dtype)
+            top, by = lead(torch.cat([Xh, tk[0, :seen, h * D:(h + 1) * D]]), q[0, hq, t], D)
+            assert top == r and by > 30, (name, r, top, by)
+            out = rtkv.extend_attention(p, q, Hkv, tail)
+            row = Y[0, r, h * D:(h + 1) * D].float()
+            err = (out[0, hq, t] - row).abs().max().item()
+            print(f"{name} (row {r} of {n}, class {int(kept_classes(pk)[r])}): lead {by:.1f} nats, "
+                  f"max |out - row| {err:.2e}")
+            torch.testing.assert_close(out[0, hq, t], row, rtol=SINGLE_RTOL, atol=SINGLE_ATOL * vmax,
+                                       msg=lambda m: f"{name}: {m}")
+
+
+# (dtype, T, G, tail counts per batch row, spare NaN rows, counts on the device as given).  Hkv = 4 (B = 1) or 8
+# (B = 2), D = 128.  Counts around the 32-key image (31, 32, 33), around four waves' images and the rows of a
+# split (127, 128, 129), around a second split (255, 257), several tail splits (1570); G·T below, at and above
+# 16 (one or two query tiles per pass) and above 32 (several passes): passes inside one GQA head (G = 4, T = 70)
+# and passes that span two (G = 2, T = 17); B = 2 with different counts and a strided tail; device-side
+# counts below T, zero, above the capacity and negative (the expectation clamps as the kernel must).
+MAPS = [
+    ("float16", 1, 1, [31], 3, None),
+    ("bfloat16", 5, 2, [32], 3, None),
+    ("float16", 16, 1, [33], 3, None),
+    ("bfloat16", 17, 2, [127], 1, None),
+    ("float16", 33, 1, [128], 1, None),
+    ("bfloat16", 70, 4, [129], 3, None),
+    ("float16", 5, 4, [255], 1, None),
+    ("bfloat16", 17, 1, [257], 3, None),
+    ("float16", 70, 2, [1570], 3, None),
+    ("bfloat16", 16, 4, [1570], 2, None),
+    ("float16", 33, 2, [129, 40], 5, None),
+    ("bfloat16", 70, 1, [64, 257], 3, None),
+    ("float16", 17, 2, [5, 0], 130, [5, 0]),
+    ("bfloat16", 33, 4, [130, 0], 0, [1130, -4]),
+]
+
+
+@pytest.mark.parametrize("dtype,T,G,counts,spare,device_counts", MAPS,
+                         ids=[f"{dt}-T{T}-G{G}-" + "-".join(map(str, dc or c)) for dt, T, G, c, _, dc in MAPS])
+def test_onehot_tail_map(dtype, T, G, counts, spare, device_counts):
+    """Zero keys and one-hot values (attn_checks.onehot_tail) and no packed row: every logit is 0, every
+    weight exactly 1 in fp32 and in the dtype, every sum a small integer, so
+    out[b, hq, t, c] = #{u < vis(b, t) : u mod 128 = c} / vis(b, t) with no tolerance: zeros exactly zero, the
+    rest within one float32 ulp (check_onehot).  A tail row skipped, read twice or shown to a query one step
+    early or late shows in its channel, at every position.  Unused rows are NaN."""
+    import rtkv
+    B, D = len(counts), 128
+    Hkv = 4 if B == 1 else 8
+    Hq, cap = Hkv * G, max(counts) + spare
+    k2, v2, pk0 = layer(B, 620 if B == 1 else 800, Hkv, D, dtype)
+    none = {k: v for k, v in pk0.items() if k != "_rows_dev"}
+    none["rows"] = [0] * B
+    tk, tv = onehot_tail(B, cap, Hkv, D, TD[dtype], counts, "cuda", spare=4 if B > 1 else 0)
+    assert B == 1 or tk.stride(0) > cap * Hkv * D
+    rows = torch.tensor(counts) if device_counts is None else torch.tensor(device_counts, device="cuda")
+    tail = rtkv.DecodeTail.from_tensors(tk, tv, rows)
+    vis = torch.stack([visible(T, n) for n in counts])[:, None, :]          # [B, 1, T]
+    q = rand(311 + T, (B, Hq, T, D), dtype)
+    for name, p in (("rows = [0]", none), ("no packed capacity", empty_packed(B, Hkv * D, dtype))):
+        out = rtkv.extend_attention(p, q, Hkv, tail)
+        assert out.shape == (B, Hq, T, D)
+        check_onehot(out, vis, name)

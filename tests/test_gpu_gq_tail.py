@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import synth
+from attn_checks import check_onehot, onehot_tail
 
 pytestmark = pytest.mark.gpu
 
@@ -207,6 +208,23 @@ def test_device_side_counts():
     out = pad.attend(q, tail=tail)
     check(out, reference(kq, vq, c.rows, tk, tv, T, q, H), vq, tv, T)
     assert torch.equal(out, c.attend(q, tail=tail))
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16", "float32"])
+def test_onehot_tail_map(dtype):
+    """The device kept count set to 0, zero tail keys and one-hot tail values (attn_checks.onehot_tail): every
+    weight is exactly 1, so out[0, hq, c] = #{u < n : u mod 128 = c} / n with no tolerance — a tail row skipped
+    or read twice shows in its channel.  Counts around the 64-row round of the four waves and with several
+    tail splits; unused rows are NaN."""
+    import rtkv
+    H, Hq, S = 4, 8, 1300
+    c, _, _, _, _ = layer(dtype, S, H, 4)
+    none = with_stats_kept(c, 0)
+    q = rand(35, (1, Hq, 128), dtype)
+    for n in (1, 3, 63, 64, 65, 257, 1500):
+        tk, tv = onehot_tail(1, n + 3, H, 128, TD[dtype], [n], "cuda")
+        out = none.attend(q, tail=rtkv.DecodeTail.from_tensors(tk, tv, torch.tensor([n])))
+        check_onehot(out, torch.tensor([[n]]), f"{dtype} n = {n}")
 
 
 def scores(kq, n, tk, t, q, H, hq):
